@@ -11,12 +11,15 @@ gradient all-reduce (N>1), gradient clipping (1.0) and AdamW.  The COO->CSR inde
 fresh sampled batch arrives every step in the reference's loader).  Default workload "c2s": 32 sampled
 subgraphs (500 target notes + [5,5] hops each) per GPU (weak scaling: per-GPU work fixed).
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 N > 1 without WORLD_SIZE in the environment: this process only spawns `python -m torch.distributed.run
 --nproc-per-node N bench.py ...` (before anything touches the GPU) and relays rank 0's JSON line and the exit
-code; under torch.distributed.run it is one rank.  Prints ONE JSON line on rank 0 with `roofline` (the
-workload's dominant hand-written aggregation kernel, HBM bound, live HIP-event timing) and `cpu_baseline`
-(oracle port on host cores).
+code; under torch.distributed.run it is one rank.  Prints ONE JSON line on rank 0.  A plain run sets up, warms up,
+times the K steps and reports them (`value`, `ms_per_step`); `--full` adds what takes work of its own: `roofline`
+(the workload's dominant hand-written aggregation kernel, HBM bound, live HIP-event timing), the step's algorithmic
+FLOPs and `mfma_frac`, `other_workloads` (default workload, one GPU) and `cpu_baseline` (oracle port on host cores).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32): the loss, the per-task
+losses, a fixed sample of rows of the logits and the parameters after the step's update.
 """
 from __future__ import annotations
 
@@ -62,35 +65,59 @@ METRICS = {"c2s": "subgraph-nodes/sec fwd+bwd, HybridGNN L=3 H=256", "c2": "subg
            "c3": "subgraph-nodes/sec fwd+bwd, HGT L=3 H=256", "c3d": "subgraph-nodes/sec fwd+bwd, HGT L=3 H=256", "c5": "subgraph-nodes/sec fwd+bwd, MetricalGNN L=4 H=512"}
 
 
+# What the timed step computes must not depend on timings taken in the run: with the same arguments every run launches the
+# same kernels in the same order, and its outputs are the same bit for bit.  So the two choices that used to be made by timing
+# at start-up are pinned.  (1) The library GEMMs: the PyTorch TunableOp selection measured once per workload on an MI355X,
+# tuning/tunableop_<workload>.csv, loaded with tuning off (`--retune-gemm` measures again).  (2) The hybrid encoders' backward
+# schedule: (sequence branch behind a late node, its deferred products with the main flush, share of the main flush's
+# products kept there) — one the start-up measurement picks on an MI355X under the pinned GEMMs (c2s: the three variants it
+# picked are within 0.3 % of each other, this one the fastest over alternating runs; `--schedule auto --items-home auto
+# --flush-keep auto` measures all 12 again).
+TUNING_DIR = os.path.join(ROOT, "tuning")
+PINNED_SCHEDULE = {"c2s": (True, True, 0.75), "c2": (False, False, 0.5), "c2d": (True, False, 0.5), "c3": (True, False, 0.5),
+                   "c3d": (False, False, 0.5)}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--steps", type=int, default=30, help="timed steps (>= 1)")
+    ap.add_argument("--warmup", type=int, default=5, help="untimed steps before the timed ones")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline, algorithmic FLOPs / mfma_frac, "
+                         "other_workloads (default workload, one GPU) and cpu_baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out cpu_baseline")
     ap.add_argument("--workload", default="c2s", choices=list(WORKLOADS),
                     help="c2s (default, the BASELINE metric on the batch a training step of the reference sees): " + WORKLOADS["c2s"] +
                          "; c2: " + WORKLOADS["c2"] + "; c3: " + WORKLOADS["c3"] + "; c5: " + WORKLOADS["c5"])
     ap.add_argument("--mt-strategy", default="wloss", choices=["wloss", "sum"],
                     help="wloss (reference CLI default): learned uncertainty weights per task; sum: plain sum of the task losses")
     ap.add_argument("--no-graph", action="store_true", help="issue every launch eagerly instead of replaying hipGraphs")
-    ap.add_argument("--schedule", default="auto", choices=["auto", "late", "plain"],
-                    help="backward schedule of the hybrid encoders: capture both and keep the faster (auto), or force one")
+    ap.add_argument("--schedule", default=None, choices=["auto", "late", "plain"],
+                    help="backward schedule of the hybrid encoders: capture both and keep the faster (auto), or force one; "
+                         "default: the workload's entry in PINNED_SCHEDULE")
     ap.add_argument("--no-defer", action="store_true", help="A/B only: weight gradients where they are computed, not deferred")
     ap.add_argument("--defer-all", action="store_true", help="A/B only: deferred (batched) weight gradients for MetricalGNN too")
     ap.add_argument("--no-wgrad-overlap", action="store_true", help="A/B only: weight gradients on the main stream")
     ap.add_argument("--force-wgrad-overlap", action="store_true", help="A/B only: the weight-gradient stream for any workload (default: c2 / c2s)")
-    ap.add_argument("--items-home", default="auto", choices=["auto", "on", "off"],
-                    help="a branch stream's deferred weight-gradient products: with the main chain's flush (on) / on the branch's own (off) / measured (auto)")
+    ap.add_argument("--items-home", default=None, choices=["auto", "on", "off"],
+                    help="a branch stream's deferred weight-gradient products: with the main chain's flush (on) / on the branch's own (off) / "
+                         "measured (auto); default: PINNED_SCHEDULE")
     ap.add_argument("--fused-heads", action="store_true", help="A/B only: the head block's forward in one launch (agnn_heads_fwd_f32)")
     ap.add_argument("--set", action="append", default=[], metavar="MODULE.NAME=VALUE",
                     help="A/B runs: set a module-level switch of the package, e.g. --set encoders.JOIN_ONE_LAUNCH=False (value: a Python literal)")
     ap.add_argument("--lr", type=float, default=5e-4, help="AdamW rate of the run (the reference's warm-up schedule at step 50 of 500: 5e-3 * 50 / 500)")
-    ap.add_argument("--flush-keep", type=float, default=None,
-                    help="share of the main flush point's weight-gradient FLOPs that runs there (rest: the sequence branch's flush); default: measured")
+    ap.add_argument("--flush-keep", default=None,
+                    help="share of the main flush point's weight-gradient FLOPs that runs there (rest: the sequence branch's flush), "
+                         "or auto (measured); default: PINNED_SCHEDULE")
     ap.add_argument("--no-yield-gemm", action="store_true", help="A/B only: the graph stack's second layer does not wait for the GRU's inner input projection")
     ap.add_argument("--no-tune-gemm", action="store_true",
-                    help="library GEMMs as hipBLASLt's heuristic picks them (default: PyTorch TunableOp times the candidates during the eager warm-up steps)")
+                    help="library GEMMs as hipBLASLt's heuristic picks them (default: the PyTorch TunableOp selection committed in tuning/)")
+    ap.add_argument("--retune-gemm", action="store_true",
+                    help="PyTorch TunableOp times the candidates during the eager warm-up steps instead of loading tuning/tunableop_<workload>.csv; "
+                         "the results file's path is printed (to refresh the committed one)")
     ap.add_argument("--side-priority", type=int, default=0, help="A/B only: HIP priority of the sequence branch's stream (-1 = high)")
     ap.add_argument("--wgrad-scope", default="sequence", help="A/B only: kinds of weight-gradient work on the side stream")
     ap.add_argument("--library-wgrad", action="store_true", help="A/B only: weight gradients through the library GEMM")
@@ -99,8 +126,15 @@ def parse_args(argv=None):
     ap.add_argument("--host-times", action="store_true", help="debugging: report the host time inside the replay calls")
     ap.add_argument("--one-bucket", action="store_true", help="N > 1, A/B only: one gradient message between the two graph replays "
                     "instead of two buckets with the first all-reduce beside the input layers' backward")
-    ap.add_argument("--no-other", action="store_true", help="skip the secondary (whole-graph C2) measurement of the default run")
-    return ap.parse_args(argv)
+    ap.add_argument("--no-other", action="store_true", help="--full: leave out the secondary workloads (other_workloads)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.flush_keep not in (None, "auto"):
+        args.flush_keep = float(args.flush_keep)
+    if args.no_tune_gemm and args.retune_gemm:
+        ap.error("--no-tune-gemm and --retune-gemm exclude each other")
+    return args
 
 
 def self_launch(args) -> int:
@@ -371,9 +405,9 @@ def main():
     if args.no_yield_gemm:
         from analysisgnn_amd import gru as _gru
         _gru.YIELD_TO_PROJECTIONS = False
-    if args.flush_keep is not None:
+    if args.flush_keep not in (None, "auto"):
         _lin.FLUSH_KEEP = args.flush_keep
-    if args.items_home != "auto":
+    if args.items_home in ("on", "off"):
         _lin.ITEMS_HOME = args.items_home == "on"
     # analysis.py:1380-1381 + train_analysisgnn.py:58-59: AdamW(lr 5e-3, weight decay 5e-3) behind a LINEAR WARM-UP over the first
     # 500 steps (analysis.py:1390-1399).  A bench run is the first ~50 steps of that schedule, where the reference's rate is
@@ -391,6 +425,8 @@ def main():
     def _lib_stamp(name):                                           # AGNN_STAMPS=1: device time stamps inside the captured step
         _agnn_lib.stamp(name, dev)
 
+    last = {}                                                       # the step's outputs (--dump-outputs): loss, per-task losses, logits
+
     def fwd_bwd():
         _lib_stamp("step start")
         flat.zero()
@@ -399,7 +435,8 @@ def main():
         x = model.encode(I["pitch_spelling"], I["key_signature"], I["x_dict"], I["edge_index_dict"], I["batch_dict"],
                          I["batch_size"], I["neighbor_mask_node"], I["neighbor_mask_edge"])      # analysis.py:953-961
         logits, offs, _ = model.forward_clf_fused(x)
-        loss, _ = training_loss(logits, offs, label_mat, x, 0.1, 0.1, -1, task_params=clf_loss.weights())   # analysis.py:1034-1036, :1072
+        loss, per_task = training_loss(logits, offs, label_mat, x, 0.1, 0.1, -1, task_params=clf_loss.weights())   # analysis.py:1034-1036, :1072
+        last.update(loss=loss.detach(), per_task=per_task.detach(), logits=logits.detach())      # detached: no autograd graph kept alive
         _lib_stamp("forward + objective issued (main)")
         loss.backward(gradient=one)                                # THE resident 1.0: no fill launch, and the objective's backward launches nothing
         flat.pack("early" if buckets else None)                    # two buckets: backward stopped behind the input layers
@@ -439,15 +476,29 @@ def main():
     # time a shape is seen — here during the eager warm-up steps — and is frozen before the step is captured.  C2 3.08 -> 3.02 ms,
     # C5 6.33 -> 6.20 (round 3; in round 2 the tuned kernels shared the chip worse with the recurrence kernels, which now keep
     # their CUs to themselves).  A library setting any user of the package can make; `--no-tune-gemm` measures without it.
+    # The selection is the one committed for the workload (TUNING_DIR), read with tuning off: timing in the run would pick
+    # different kernels from run to run, and with them different rounding.  `--retune-gemm` (or a file that does not load, e.g.
+    # written under other library versions) times the candidates in the run, as the selection was made.
     gemm_selection = "hipBLASLt heuristic"
     if not args.no_tune_gemm:
         try:
             import tempfile
             _tn = torch.cuda.tunable
+            # results measured in this run (--retune-gemm) are written here at exit; the committed file is only read
             _tn.set_filename(os.path.join(tempfile.gettempdir(), f"agnn_tunableop_{args.workload}_r{rank}.csv"))
             _tn.enable(True)
-            _tn.tuning_enable(True)
-            gemm_selection = "hipBLASLt via PyTorch TunableOp (candidates timed during the eager warm-up steps, frozen before capture)"
+            pinned = os.path.join(TUNING_DIR, f"tunableop_{args.workload}.csv")
+            if not args.retune_gemm and os.path.exists(pinned) and _tn.read_file(pinned):
+                _tn.tuning_enable(False)
+                gemm_selection = f"hipBLASLt via PyTorch TunableOp (selection read from tuning/{os.path.basename(pinned)}, no tuning in the run)"
+            else:
+                if not args.retune_gemm:
+                    print(f"[bench] {pinned} missing or not loadable here: timing the GEMM candidates in this run "
+                          f"(the outputs then depend on what the timing picks)", file=sys.stderr)
+                _tn.tuning_enable(True)
+                gemm_selection = "hipBLASLt via PyTorch TunableOp (candidates timed during the eager warm-up steps, frozen before capture)"
+                if rank == 0:
+                    print(f"[bench] TunableOp results of this run: {_tn.get_filename()}", file=sys.stderr)
         except Exception as e:                                   # an older torch: measured as the heuristic picks
             print(f"[bench] TunableOp unavailable ({type(e).__name__}: {e})", file=sys.stderr)
 
@@ -475,11 +526,18 @@ def main():
             # them in the main chain's flush, c2d 3.38 vs 3.35 — round 3, alternating pairs on one box).
             from analysisgnn_amd import encoders as _enc
             hybrid = enc in ("hybridgnn", "hgt") and not args.no_defer and not dot
-            lates = [True, False] if args.schedule == "auto" and hybrid else [{"late": True, "plain": False, "auto": _enc.LATE_SEQUENCE_BACKWARD}[args.schedule]]
-            homes = [True, False] if args.items_home == "auto" and hybrid else [_lin.ITEMS_HOME]
+            # By default each choice is the workload's pinned one (PINNED_SCHEDULE: no timing decides what is replayed); "auto" measures.
+            pin = PINNED_SCHEDULE.get(args.workload) if hybrid else None
+            if args.schedule == "auto" and hybrid:
+                lates = [True, False]
+            elif args.schedule in ("late", "plain"):
+                lates = [args.schedule == "late"]
+            else:
+                lates = [pin[0] if pin else _enc.LATE_SEQUENCE_BACKWARD]
+            homes = [True, False] if args.items_home == "auto" and hybrid else [pin[1] if pin and args.items_home is None else _lin.ITEMS_HOME]
             # ... and for how much of the main flush point's weight-gradient work runs there: since the recurrence kernels got
             # shorter (round 3) the main chain's flush outlasts the sequence branch, whose stream then has room for the rest
-            keeps = [1.0, 0.75, 0.5] if args.flush_keep is None and hybrid else [_lin.FLUSH_KEEP]
+            keeps = [1.0, 0.75, 0.5] if args.flush_keep == "auto" and hybrid else [pin[2] if pin and args.flush_keep is None else _lin.FLUSH_KEEP]
             variants = [(a, b, k) for a in lates for b in homes for k in keeps]
             best = None
             # every captured variant stays alive to the end of the run: letting the losers be destroyed (hipGraphExecDestroy + their
@@ -510,8 +568,10 @@ def main():
                     t_v = dp.max_over_ranks(time.perf_counter() - t0)
                 keep_alive.append((g1, gt))
                 if best is None or t_v < best[0]:
-                    best = (t_v, g1, loss_v, late, gt, home, keep)
-            _, g1, loss_ref[0], schedule_late, g_tail, schedule_home, schedule_keep = best
+                    best = (t_v, g1, loss_v, late, gt, home, keep, dict(last))
+            _, g1, loss_ref[0], schedule_late, g_tail, schedule_home, schedule_keep, best_last = best
+            last.clear()
+            last.update(best_last)                              # the kept graph's outputs, rewritten by each of its replays
             _enc.LATE_SEQUENCE_BACKWARD, _lin.ITEMS_HOME, _lin.FLUSH_KEEP = schedule_late, schedule_home, schedule_keep
             if rank == 0 and len(variants) > 1:
                 print(f"[bench] backward schedule: sequence branch {'behind a late node' if schedule_late else 'in autograd order'}, "
@@ -582,11 +642,13 @@ def main():
     assert torch.isfinite(loss).item(), "loss diverged"
     from analysisgnn_amd import _lib
     _lib.check_device_status(dev)                      # no CSR build of the run flagged an inconsistent index (outside the timed region)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, trainable)
 
     if sampler is not None:                                         # the roofline launch runs on the LAST sampled batch
         g.edge_index = {et: e.cpu().numpy() for et, e in I["edge_index_dict"].items()}
         g.num_nodes = {t: int(v.shape[0]) for t, v in I["x_dict"].items()}
-    roof = roofline(args.workload, g, I, hid, layers, dev) if rank == 0 else None
+    roof = roofline(args.workload, g, I, hid, layers, dev) if rank == 0 and args.full else None
     if rank == 0:
         nodes = I["batch_size"] * world * args.steps
         e_tot = sum(int((e[0] >= 0).sum()) for e in g.edge_index.values())
@@ -612,24 +674,27 @@ def main():
                        "allreduce": ("none (one rank)" if world == 1 else
                                      f"2 buckets: {flat.cut} floats shipped asynchronously beside the input layers' backward, then "
                                      f"{flat.flat.numel() - flat.cut}; SUM / world" if buckets else "one message between the two graph replays")},
-            "roofline": roof,
         }
-        # whole-step efficiency as a reported number: algorithmic matrix FLOPs of the step / step time / fp32-MFMA peak
-        fl, parts = algorithmic_flops(enc, I, hid, layers, tasks)
-        out["step_flops_alg"] = fl
-        out["mfma_frac"] = fl / (dt / args.steps) / MFMA_F32_PEAK
-        out["step_flops_breakdown"] = {k: round(v / 1e9, 3) for k, v in parts.items()}     # GFLOP per step (fwd + bwd)
-        if world == 1 and args.workload == "c2s" and not args.no_other:
+        if args.full:
+            out["roofline"] = roof
+            # whole-step efficiency as a reported number: algorithmic matrix FLOPs of the step / step time / fp32-MFMA peak
+            fl, parts = algorithmic_flops(enc, I, hid, layers, tasks)
+            out["step_flops_alg"] = fl
+            out["mfma_frac"] = fl / (dt / args.steps) / MFMA_F32_PEAK
+            out["step_flops_breakdown"] = {k: round(v / 1e9, 3) for k, v in parts.items()}     # GFLOP per step (fwd + bwd)
+        if args.full and world == 1 and args.workload == "c2s" and not args.no_other:
             # secondary figures, each a child process with the same steps: "c2" = continuity with round 1's line (whole graphs,
             # nothing trimmed); "c2d" = the same training step with the batch sampled and gathered ON THE DEVICE inside it
             out["other_workloads"] = {}
             for wl in ("c2", "c2d", "c3", "c3d", "c5"):
                 r = None
                 try:
-                    cmd = [sys.executable, "-X", "faulthandler", os.path.abspath(__file__), "--workload", wl, "--no-cpu-baseline", "--steps",
+                    cmd = [sys.executable, "-X", "faulthandler", os.path.abspath(__file__), "--workload", wl, "--full", "--no-cpu-baseline", "--steps",
                            str(args.steps), "--warmup", str(args.warmup), "--mt-strategy", args.mt_strategy]
                     if args.no_tune_gemm:
                         cmd.append("--no-tune-gemm")
+                    if args.retune_gemm:
+                        cmd.append("--retune-gemm")
                     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
                     o = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
                     out["other_workloads"][wl] = {"metric": o["metric"], "value": o["value"], "ms_per_step": o["ms_per_step"],
@@ -638,11 +703,38 @@ def main():
                 except Exception as e:                              # secondary figures only; say why (the child's last lines)
                     why = " | ".join((r.stderr or "").strip().splitlines()[-6:]) if r is not None else ""
                     out["other_workloads"][wl] = f"not measured ({type(e).__name__}; exit code {getattr(r, 'returncode', None)}; {why[-600:]})"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, args.mt_strategy)
         print(json.dumps(out))
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+DUMP_LOGIT_ROWS = 2048        # --dump-outputs: rows of the logits written (a fixed, seeded sample)
+
+
+def dump_outputs(path: str, last: dict, trainable) -> None:
+    """--dump-outputs: what the last timed step computed, as float32 .npy files under `path` (~17 MB at c2s):
+    loss [1], task_losses [T] (mean cross entropy per task), logits_rows [R] + logits_sample [R, sum C] (R rows drawn
+    with a fixed seed; all rows when there are fewer), params [P] (every parameter after the step's update, flattened and
+    concatenated in `named_parameters` order).  With the same arguments runs repeat these bit for bit: the inputs are seeded and
+    nothing in the timed path is chosen by timing (TUNING_DIR, PINNED_SCHEDULE)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    logits = last["logits"].detach()
+    n = logits.shape[0]
+    rows = (np.sort(np.random.default_rng(0).choice(n, DUMP_LOGIT_ROWS, replace=False)) if n > DUMP_LOGIT_ROWS
+            else np.arange(n))
+    arrays = {
+        "loss": last["loss"].detach().reshape(1),
+        "task_losses": last["per_task"].detach().reshape(-1),
+        "logits_rows": torch.from_numpy(rows),
+        "logits_sample": logits[torch.from_numpy(rows).to(logits.device)],
+        "params": torch.cat([p.detach().reshape(-1) for _, p in trainable.named_parameters()]),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
 
 
 def roofline(workload, g, I, hid, layers, dev):
