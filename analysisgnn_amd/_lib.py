@@ -128,9 +128,6 @@ SIGNATURES = {
     "agnn_hgt_attn_bwd_dst_f32": (C.c_int, [C.c_int, C.POINTER(HgtRel), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                             C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
-    "agnn_hgt_attn_bwd_src_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
-                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "agnn_hgt_attn_bwd_src_batch_f32": (C.c_int, [C.c_int32, C.POINTER(HgtSrcItem), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                   C.c_int32, C.c_int32, C.c_void_p]),
     "agnn_sampler_num_nodes": (C.c_int64, [C.POINTER(Sampler)]),

@@ -334,15 +334,6 @@ __device__ __forceinline__ void hgt_bwd_src_rows(const int32_t* __restrict__ row
   }
 }
 
-template <int CH>
-__global__ __launch_bounds__(256) void k_hgt_bwd_src(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rowend,
-                                                     const int32_t* __restrict__ col, const int32_t* __restrict__ perm,
-                                                     const float* __restrict__ alpha, const float* __restrict__ gs, HgtArgs a,
-                                                     const float* __restrict__ dm, int64_t ld_dm, float* __restrict__ dk,
-                                                     float* __restrict__ dv, int64_t ld_o) {
-  hgt_bwd_src_rows<CH>(rowptr, rowend, col, perm, alpha, gs, a, dm, ld_dm, dk, dv, ld_o, blockIdx.x, gridDim.x);
-}
-
 // All relations that end in one destination type in ONE launch (they share q and dM; each writes its own column block of its
 // source type's dK' / dV'): as separate launches they were four ~13 us kernels in a row on the HGT stack's backward chain.
 struct SrcBatch {
@@ -468,25 +459,6 @@ extern "C" int agnn_hgt_attn_bwd_dst_f32(int n_rel, const agnn_hgt_rel_t* rels, 
   else if (H <= 512) hipLaunchKernelGGL(k_hgt_bwd_dst<2>, grid, block, 0, s, t, a, dm, ld_dm, out, ld_out, m_in, linv_in, dq, ld_dq);
   else hipLaunchKernelGGL(k_hgt_bwd_dst<4>, grid, block, 0, s, t, a, dm, ld_dm, out, ld_out, m_in, linv_in, dq, ld_dq);
   return check_launch("hgt_bwd_dst");
-}
-
-extern "C" int agnn_hgt_attn_bwd_src_f32(const int32_t* rowptr, const int32_t* rowend, const int32_t* col, const int32_t* perm,
-                                         const float* alpha, const float* gs, const float* q, int64_t ld_q, const float* dm,
-                                         int64_t ld_dm, int64_t n_src_rows, int32_t col_limit, int32_t H, int32_t heads,
-                                         float* dk, float* dv, int64_t ld_o, agnn_stream_t stream_) {
-  using namespace agnn;
-  if (int rc = check_shape("hgt_bwd_src", n_src_rows, H, heads)) return rc;
-  if (n_src_rows == 0) return AGNN_OK;
-  if (!rowptr || !dk || !dv) return fail(AGNN_EINVAL, "hgt_bwd_src: null argument");
-  if (!aligned16(dk) || !aligned16(dv) || (ld_o & 3) || (q && (!aligned16(q) || (ld_q & 3))) || (dm && (!aligned16(dm) || (ld_dm & 3))))
-    return fail(AGNN_EALIGN, "hgt_bwd_src: misaligned matrix");
-  HgtArgs a{q, ld_q, static_cast<int32_t>(n_src_rows), H, heads, col_limit};
-  hipStream_t s = static_cast<hipStream_t>(stream_);
-  const dim3 grid(grid_for(n_src_rows)), block(256);
-  if (H <= 256) hipLaunchKernelGGL(k_hgt_bwd_src<1>, grid, block, 0, s, rowptr, rowend, col, perm, alpha, gs, a, dm, ld_dm, dk, dv, ld_o);
-  else if (H <= 512) hipLaunchKernelGGL(k_hgt_bwd_src<2>, grid, block, 0, s, rowptr, rowend, col, perm, alpha, gs, a, dm, ld_dm, dk, dv, ld_o);
-  else hipLaunchKernelGGL(k_hgt_bwd_src<4>, grid, block, 0, s, rowptr, rowend, col, perm, alpha, gs, a, dm, ld_dm, dk, dv, ld_o);
-  return check_launch("hgt_bwd_src");
 }
 
 extern "C" int agnn_hgt_attn_bwd_src_batch_f32(int32_t n_items, const agnn_hgt_src_item_t* items, const float* q, int64_t ld_q,

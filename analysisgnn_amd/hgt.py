@@ -2,8 +2,9 @@
 layer stack, and the `HybridHGT` encoder the reference constructs at
 analysisgnn/models/analysis.py:445-453 (`heads=4`).  The per-edge work (scores, edge softmax over all
 incoming relations, weighted sum, and their gradients) runs on the C-ABI kernels
-`agnn_hgt_attn_*`; the per-type K/Q/V and output projections and the per-(relation, head) D x D
-transforms are library GEMMs.  Build-spec notes (parity unpinned vs graphmuse): encoders.py header."""
+`agnn_hgt_attn_*`, the per-(relation, head) D x D transforms on `agnn_relt_*` (at D = 64; torch batched
+matmuls at the other head widths), the per-type K/Q/V and output projections on `linear`.  Build-spec notes
+(parity unpinned vs graphmuse): encoders.py header."""
 from __future__ import annotations
 
 import contextlib
@@ -16,22 +17,12 @@ import torch.nn.functional as F
 
 from . import _lib
 from .encoders import TrimPlan, _HybridMixin
-from .graph import Csr, HeteroIndex, hetero_index
+from .graph import HeteroIndex, hetero_index
 from .fused import skip_act
 from .linear import all_steal, defer, deferring, leaf_refs, linear
 from .params import cat_rows, pack
 
 EdgeType = Tuple[str, str, str]
-
-
-class _AttnSpec:
-    def __init__(self, fwd: List[Csr], bwd: List[Csr], n_rows: int, heads: int, n_edges: List[int],
-                 e_limit: Optional[List[Optional[int]]], src_rows: List[int]):
-        self.fwd, self.bwd, self.n_rows, self.heads = fwd, bwd, n_rows, heads
-        self.n_edges, self.e_limit, self.src_rows = n_edges, e_limit, src_rows
-
-    def limit(self, r):
-        return None if self.e_limit is None else self.e_limit[r]
 
 
 def _mat(t: torch.Tensor) -> torch.Tensor:
@@ -40,141 +31,6 @@ def _mat(t: torch.Tensor) -> torch.Tensor:
     if t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
         t = t.contiguous()
     return t
-
-
-class _HGTAttention(torch.autograd.Function):
-    """M = edge_softmax_attention(q; {k'_r, v'_r}); inputs: q [N_d,H], pscale [R,heads], then k'_0, v'_0, k'_1, ..."""
-
-    @staticmethod
-    def forward(ctx, spec: _AttnSpec, q, pscale, *kv):
-        dev = _lib.require_gpu(q, pscale, *kv)
-        lib = _lib.load()
-        R = len(spec.fwd)
-        n, H, heads = spec.n_rows, q.shape[1], spec.heads
-        q = _mat(q)
-        pscale = pscale.contiguous()
-        ks = [_mat(kv[2 * r]) for r in range(R)]
-        vs = [_mat(kv[2 * r + 1]) for r in range(R)]
-        out = torch.empty((n, H), dtype=torch.float32, device=dev)
-        m = torch.empty((max(n, 1), heads), dtype=torch.float32, device=dev)
-        linv = torch.empty((max(n, 1), heads), dtype=torch.float32, device=dev)
-        rels = (_lib.HgtRel * max(R, 1))()
-        keep = []
-        for r in range(R):
-            c = spec.fwd[r]
-            re = c.rowend(spec.limit(r))
-            keep.append(re)
-            if ks[r].stride(0) != vs[r].stride(0):
-                vs[r] = vs[r].contiguous()
-                ks[r] = ks[r].contiguous()
-            rels[r].k, rels[r].v = ks[r].data_ptr(), vs[r].data_ptr()
-            rels[r].rowptr, rels[r].rowend = c.rowptr.data_ptr(), _lib.ptr(re)
-            rels[r].col, rels[r].perm = c.col.data_ptr(), c.perm.data_ptr()
-            rels[r].pscale = pscale[r].data_ptr()
-            rels[r].ld = ks[r].stride(0)
-        if n > 0:
-            _lib.check(lib.agnn_hgt_attn_fwd_f32(R, rels, q.data_ptr(), q.stride(0), n, H, heads, out.data_ptr(),
-                                                 out.stride(0), m.data_ptr(), linv.data_ptr(), _lib.stream_ptr(dev)),
-                       "agnn_hgt_attn_fwd_f32")
-        ctx.spec = spec
-        ctx.save_for_backward(q, pscale, out, m, linv, *ks, *vs)
-        return out
-
-    @staticmethod
-    def backward(ctx, dm):
-        spec: _AttnSpec = ctx.spec
-        q, pscale, out, m, linv, *rest = ctx.saved_tensors
-        R = len(spec.fwd)
-        ks, vs = rest[:R], rest[R:]
-        dev = dm.device
-        lib = _lib.load()
-        n, H, heads = spec.n_rows, q.shape[1], spec.heads
-        dm = _mat(dm)
-        dq = torch.empty_like(q) if n == q.shape[0] else torch.zeros_like(q)
-        # per-edge arrays of all relations in three allocations; only tdot is summed over ALL edges (trimmed ones
-        # included), so only it needs zeros — alpha / gs are read back solely at positions the kernel wrote
-        ne = [max(spec.n_edges[r], 1) for r in range(R)]
-        offs = [0]
-        for k_ in ne:
-            offs.append(offs[-1] + k_)
-        a_all = torch.empty((offs[-1], heads), dtype=torch.float32, device=dev)
-        g_all = torch.empty((offs[-1], heads), dtype=torch.float32, device=dev)
-        alpha = [a_all[offs[r]:offs[r + 1]] for r in range(R)]
-        gs = [g_all[offs[r]:offs[r + 1]] for r in range(R)]
-        # tdot as [R, max E_r, heads] (zero padded): the per-relation sums over edges are ONE reduction instead of R
-        t3 = torch.zeros((max(R, 1), max(ne) if ne else 1, heads), dtype=torch.float32, device=dev)
-        tdot = [t3[r, :ne[r]] for r in range(R)]
-        rels = (_lib.HgtRel * max(R, 1))()
-        keep = []
-        for r in range(R):
-            c = spec.fwd[r]
-            re = c.rowend(spec.limit(r))
-            keep.append(re)
-            rels[r].k, rels[r].v = ks[r].data_ptr(), vs[r].data_ptr()
-            rels[r].rowptr, rels[r].rowend = c.rowptr.data_ptr(), _lib.ptr(re)
-            rels[r].col, rels[r].perm = c.col.data_ptr(), c.perm.data_ptr()
-            rels[r].pscale = pscale[r].data_ptr()
-            rels[r].ld = ks[r].stride(0)
-            rels[r].alpha, rels[r].gs, rels[r].tdot = alpha[r].data_ptr(), gs[r].data_ptr(), tdot[r].data_ptr()
-        if n > 0:
-            _lib.check(lib.agnn_hgt_attn_bwd_dst_f32(R, rels, q.data_ptr(), q.stride(0), dm.data_ptr(), dm.stride(0),
-                                                     out.data_ptr(), out.stride(0), m.data_ptr(), linv.data_ptr(), n, H,
-                                                     heads, dq.data_ptr(), dq.stride(0), _lib.stream_ptr(dev)),
-                       "agnn_hgt_attn_bwd_dst_f32")
-        dps = t3.sum(dim=1) if R else torch.zeros_like(pscale)
-        grads = []
-        for r in range(R):
-            c = spec.bwd[r]
-            n_src = spec.src_rows[r]
-            dk = torch.empty((n_src, H), dtype=torch.float32, device=dev)
-            dv = torch.empty((n_src, H), dtype=torch.float32, device=dev)
-            re = c.rowend(spec.limit(r))
-            lim = n if spec.fwd[r].n_rows > n else _lib.INT32_MAX
-            if n_src > 0:
-                _lib.check(lib.agnn_hgt_attn_bwd_src_f32(c.rowptr.data_ptr(), _lib.ptr(re), c.col.data_ptr(),
-                                                         c.perm.data_ptr(), alpha[r].data_ptr(), gs[r].data_ptr(),
-                                                         q.data_ptr(), q.stride(0), dm.data_ptr(), dm.stride(0), n_src, lim,
-                                                         H, heads, dk.data_ptr(), dv.data_ptr(), dk.stride(0),
-                                                         _lib.stream_ptr(dev)), "agnn_hgt_attn_bwd_src_f32")
-            grads += [dk, dv]
-        return (None, dq, dps, *grads)
-
-
-class _ColSplit(torch.autograd.Function):
-    """G column blocks of a [N, G*H] matrix as views (row stride G*H, no copies).  Plain slicing would make autograd
-    materialise one zero-filled [N, G*H] gradient per block and add them up; here the backward gathers the blocks'
-    gradients into one [N, G*H] buffer with a single `agnn_pack_f32` launch."""
-
-    @staticmethod
-    def forward(ctx, big, G: int):
-        N, W = big.shape
-        ctx.meta = (N, W, G)
-        ctx.set_materialize_grads(False)           # unused blocks: zero-filled in place below, not as separate tensors first
-        H = W // G
-        return tuple(big[:, g * H:(g + 1) * H] for g in range(G))
-
-    @staticmethod
-    def backward(ctx, *grads):
-        N, W, G = ctx.meta
-        H = W // G
-        ref = next((g for g in grads if g is not None), None)
-        if ref is None:
-            return None, None
-        dbig = torch.empty((N, W), dtype=torch.float32, device=ref.device)
-        items = []
-        for g_i, g in enumerate(grads):
-            blk = dbig[:, g_i * H:(g_i + 1) * H]
-            if g is None:
-                blk.zero_()
-            elif N > 0:
-                items.append((blk, [_mat(g)]))
-        if items:
-            pack(items, ref.device)
-        return dbig, None
-
-
-def col_split(big: torch.Tensor, G: int):
-    return _ColSplit.apply(big, G)
 
 
 class _DictLinear(nn.Module):
@@ -207,37 +63,8 @@ def _index_tensor(ids: tuple, device) -> torch.Tensor:
     return _SEL_CACHE[key]
 
 
-class _BlockDiagWeight(torch.autograd.Function):
-    """The operand of x W^T for the relations `rel_ids` leaving one source type: row block r holds (blockdiag_h A_{r,h})^T,
-    i.e. out[r*H + h*D + j, h*D + i] = weight[rel_ids[r]*heads + h, i, j] and zeros elsewhere, so that
-    (x W^T)[:, r*H:(r+1)*H] = concat_h(x_h A_{r,h}).  Three launches forward (zeros, gather, block scatter), three
-    backward (gather of the diagonal blocks, zeros, scatter) — plain indexing costs ~15 and its autograd chain as many."""
-
-    @staticmethod
-    def forward(ctx, weight, rel_ids: tuple, n_rel: int, heads: int, D: int):
-        dev = weight.device
-        R, H = len(rel_ids), heads * D
-        sel = _index_tensor(tuple(r * heads + h for r in rel_ids for h in range(heads)), dev)      # [R*heads]
-        blocks = weight.detach().index_select(0, sel).view(R, heads, D, D)                         # A_{r,h}[i, j]
-        out = weight.new_zeros((R, heads, D, heads, D))                                             # [r, h, j, h', i]
-        ar = _arange(heads, dev)
-        out[:, ar, :, ar, :] = blocks.permute(1, 0, 3, 2)                                           # (h, r, j, i) -> out[r, h, j, h, i]
-        ctx.sel, ctx.meta = sel, (R, heads, D, weight.shape[0])
-        return out.view(R * H, H)
-
-    @staticmethod
-    def backward(ctx, g):
-        R, heads, D, T = ctx.meta
-        ar = _arange(heads, g.device)
-        gb = g.reshape(R, heads, D, heads, D)[:, ar, :, ar, :]                                      # [h, r, j, i]
-        gw = g.new_zeros((T, D, D))
-        gw.index_copy_(0, ctx.sel, gb.permute(1, 0, 3, 2).reshape(R * heads, D, D))                # back to [r*heads + h, i, j]
-        return gw, None, None, None, None
-
-
+HEAD_WIDTHS = (4, 8, 16, 32, 64, 128, 256)    # the head widths D the attention kernels take (csrc/hgt.hip check_shape)
 RELT_D = 64           # the head width the relation-transform kernels are built for (csrc/relt.hip)
-RELT_ENABLED = True   # A/B switch: False = round 1's dense GEMM against a block-diagonal weight
-CORE_ENABLED = True   # A/B switch: False = one autograd node per relation / destination type (round 1's graph)
 ATTN_ONE_LAUNCH = True  # A/B switch (bench.py --set hgt.ATTN_ONE_LAUNCH=False): the destination types' forward attention in one launch
 TYPE_STREAMS = True   # A/B switch (bench.py --set hgt.TYPE_STREAMS=False): the small node types' projections on a second stream
 _TYPE_STREAM: dict = {}
@@ -251,63 +78,43 @@ def _type_stream(dev) -> "torch.cuda.Stream":
     return s
 
 
-class _RelTransform(torch.autograd.Function):
-    """(k', v') for the relations `rel_ids` leaving one source type: k'[:, r*H + h*D + j] = sum_i k[:, h*D + i] *
-    k_rel.weight[rel_ids[r]*heads + h, i, j] (same for v) — `agnn_relt_*`: R*heads independent D x D products per operand on
-    the fp32 MFMA, K and V in one launch, instead of one dense [N, H] x [H, R*H] GEMM against a block-diagonal weight
-    (heads x the useful FLOPs) and the launches that assemble it."""
+def _relt(op: str, items, R: int, heads: int, D: int, dev) -> None:
+    """The per-(relation, head) D x D relation transforms of one source type, written in place for both (a, b, y) of `items`
+    (K and V); block (r, h) is columns (r*heads + h)*D .. +D of an [N, R*H] operand, columns h*D .. +D of an [N, H] one:
+      fwd  y_rh = a_h @ b[r*heads + h]                  a = x [N, H], b = weight blocks [R*heads, D, D], y = x' [N, R*H]
+      bwd  y_h = sum_r a_rh @ b[r*heads + h]            a = dx' [N, R*H], b = TRANSPOSED weight blocks, y = dx [N, H]
+      dw   y[r*heads + h] = a_h^T @ b_rh                a = x [N, H], b = dx' [N, R*H], y = weight-block gradients [R*heads, D, D]
+    `agnn_relt_<op>_f32` at D = RELT_D, the width those kernels are built for; torch batched matmuls at any other head width."""
+    N = items[0][0].shape[0]
+    if D != RELT_D:
+        for a, b, y in items:
+            if op == "fwd":
+                y.view(N, R, heads, D).copy_(torch.einsum("nhi,rhij->nrhj", a.view(N, heads, D), b.view(R, heads, D, D)))
+            elif op == "bwd":
+                y.view(N, heads, D).copy_(torch.einsum("nrhi,rhij->nhj", a.view(N, R, heads, D), b.view(R, heads, D, D)))
+            else:
+                y.view(R, heads, D, D).copy_(torch.einsum("nhi,nrhj->rhij", a.view(N, heads, D), b.view(N, R, heads, D)))
+        return
+    lib = _lib.load()
+    arr = (_lib.ReltItem * 2)()
+    for it, (a, b, y) in zip(arr, items):
+        it.x, it.w, it.y, it.ld_x, it.ld_y = a.data_ptr(), b.data_ptr(), y.data_ptr(), a.stride(0), (b if op == "dw" else y).stride(0)
+    if op == "dw":
+        nws = int(lib.agnn_relt_dw_workspace_bytes(2, R, heads, D, N))
+        ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
+        _lib.check(lib.agnn_relt_dw_f32(2, arr, R, heads, D, N, ws.data_ptr(), nws, _lib.stream_ptr(dev)), "agnn_relt_dw_f32")
+    else:
+        fn = lib.agnn_relt_fwd_f32 if op == "fwd" else lib.agnn_relt_bwd_f32
+        _lib.check(fn(2, arr, R, heads, D, N, _lib.stream_ptr(dev)), f"agnn_relt_{op}_f32")
 
-    @staticmethod
-    def forward(ctx, k, v, wk, wv, rel_ids: tuple, heads: int, D: int):
-        dev = _lib.require_gpu(k, v, wk, wv)
-        lib = _lib.load()
-        k, v = _mat(k), _mat(v)
-        R, H, N = len(rel_ids), heads * D, k.shape[0]
-        sel = _index_tensor(tuple(r * heads + h for r in rel_ids for h in range(heads)), dev)
-        Wk = wk.detach().index_select(0, sel)                     # [R*heads, D, D], contiguous
-        Wv = wv.detach().index_select(0, sel)
-        yk = torch.empty((N, R * H), dtype=torch.float32, device=dev)
-        yv = torch.empty((N, R * H), dtype=torch.float32, device=dev)
-        items = (_lib.ReltItem * 2)()
-        for it, (x, w, y) in zip(items, ((k, Wk, yk), (v, Wv, yv))):
-            it.x, it.w, it.y, it.ld_x, it.ld_y = x.data_ptr(), w.data_ptr(), y.data_ptr(), x.stride(0), y.stride(0)
-        if N > 0:
-            _lib.check(lib.agnn_relt_fwd_f32(2, items, R, heads, D, N, _lib.stream_ptr(dev)), "agnn_relt_fwd_f32")
-        ctx.save_for_backward(k, v, Wk, Wv, sel)
-        ctx.meta = (R, heads, D, tuple(wk.shape), tuple(wv.shape))
-        return yk, yv
 
-    @staticmethod
-    def backward(ctx, dyk, dyv):
-        k, v, Wk, Wv, sel = ctx.saved_tensors
-        R, heads, D, wk_shape, wv_shape = ctx.meta
-        dev = k.device
-        lib = _lib.load()
-        N, H = k.shape[0], heads * D
-        zk = dyk is None
-        dyk = _mat(dyk) if dyk is not None else torch.zeros((N, R * H), dtype=torch.float32, device=dev)
-        dyv = _mat(dyv) if dyv is not None else torch.zeros((N, R * H), dtype=torch.float32, device=dev)
-        dk = dv = gwk = gwv = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            dk = torch.empty((N, H), dtype=torch.float32, device=dev)
-            dv = torch.empty((N, H), dtype=torch.float32, device=dev)
-            Wkt, Wvt = Wk.transpose(1, 2).contiguous(), Wv.transpose(1, 2).contiguous()
-            items = (_lib.ReltItem * 2)()
-            for it, (x, w, y) in zip(items, ((dyk, Wkt, dk), (dyv, Wvt, dv))):
-                it.x, it.w, it.y, it.ld_x, it.ld_y = x.data_ptr(), w.data_ptr(), y.data_ptr(), x.stride(0), y.stride(0)
-            if N > 0:
-                _lib.check(lib.agnn_relt_bwd_f32(2, items, R, heads, D, N, _lib.stream_ptr(dev)), "agnn_relt_bwd_f32")
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            dWk, dWv = torch.empty_like(Wk), torch.empty_like(Wv)
-            nws = int(lib.agnn_relt_dw_workspace_bytes(2, R, heads, D, N))
-            ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
-            items = (_lib.ReltItem * 2)()
-            for it, (x, dy, y) in zip(items, ((k, dyk, dWk), (v, dyv, dWv))):
-                it.x, it.w, it.y, it.ld_x, it.ld_y = x.data_ptr(), dy.data_ptr(), y.data_ptr(), x.stride(0), dy.stride(0)
-            _lib.check(lib.agnn_relt_dw_f32(2, items, R, heads, D, N, ws.data_ptr(), nws, _lib.stream_ptr(dev)), "agnn_relt_dw_f32")
-            gwk = torch.zeros(wk_shape, dtype=torch.float32, device=dev).index_copy_(0, sel, dWk)
-            gwv = torch.zeros(wv_shape, dtype=torch.float32, device=dev).index_copy_(0, sel, dWv)
-        return dk, dv, gwk, gwv, None, None, None
+def attention_forward(rels, q: torch.Tensor, out: torch.Tensor, m: torch.Tensor, linv: torch.Tensor, heads: int) -> None:
+    """One `k_hgt_fwd` launch (`agnn_hgt_attn_fwd_f32`): the edge-softmax attention of the out.shape[0] rows of one destination
+    type over the relations of the `_lib.HgtRel` table `rels`.  q [n, H] (a column view is fine), out [n, H]; m / linv [n, heads]
+    receive the softmax statistics the backward pass reads."""
+    n, H = out.shape
+    _lib.check(_lib.load().agnn_hgt_attn_fwd_f32(len(rels), rels, q.data_ptr(), q.stride(0), n, H, heads, out.data_ptr(), out.stride(0),
+                                                 m.data_ptr(), linv.data_ptr(), _lib.stream_ptr(out.device)), "agnn_hgt_attn_fwd_f32")
 
 
 class _CorePlan:
@@ -356,10 +163,7 @@ class _HGTCore(torch.autograd.Function):
             kp[s_t] = torch.empty((N, R * H), dtype=torch.float32, device=dev)
             vp[s_t] = torch.empty((N, R * H), dtype=torch.float32, device=dev)
             if N > 0:
-                items = (_lib.ReltItem * 2)()
-                for it, (off, w, y) in zip(items, ((0, Wk[s_t], kp[s_t]), (2 * H, Wv[s_t], vp[s_t]))):
-                    it.x, it.w, it.y, it.ld_x, it.ld_y = x.data_ptr() + 4 * off, w.data_ptr(), y.data_ptr(), x.stride(0), y.stride(0)
-                _lib.check(lib.agnn_relt_fwd_f32(2, items, R, heads, D, N, _lib.stream_ptr(dev)), "agnn_relt_fwd_f32")
+                _relt("fwd", ((x[:, :H], Wk[s_t], kp[s_t]), (x[:, 2 * H:], Wv[s_t], vp[s_t])), R, heads, D, dev)
         ps = (p_all.detach() * (1.0 / math.sqrt(D))).contiguous()                   # [n_edge_types, heads]
         outs, stats = [], {}
         live = [t for t in plan.types if plan.dst_rels.get(t) and plan.n_of[t] > 0]
@@ -385,8 +189,7 @@ class _HGTCore(torch.autograd.Function):
                 it.out, it.ld_out, it.m_out, it.linv_out = out.data_ptr(), out.stride(0), m.data_ptr(), linv.data_ptr()
                 hold.append((arr, keep))
             else:
-                _lib.check(lib.agnn_hgt_attn_fwd_f32(len(rels), arr, q.data_ptr() + 4 * H, q.stride(0), n, H, heads, out.data_ptr(),
-                                                     out.stride(0), m.data_ptr(), linv.data_ptr(), _lib.stream_ptr(dev)), "agnn_hgt_attn_fwd_f32")
+                attention_forward(arr, q[:, H:2 * H], out, m, linv, heads)
             stats[t] = (m, linv)
             outs.append(out)
         if one_launch:
@@ -536,10 +339,7 @@ class _HGTCore(torch.autograd.Function):
             dx = dkqv[s_t]
             if N > 0:
                 Wkt, Wvt = Wk[s_t].transpose(1, 2).contiguous(), Wv[s_t].transpose(1, 2).contiguous()
-                items = (_lib.ReltItem * 2)()
-                for it, (dy, w, off) in zip(items, ((dkp[s_t], Wkt, 0), (dvp[s_t], Wvt, 2 * H))):
-                    it.x, it.w, it.y, it.ld_x, it.ld_y = dy.data_ptr(), w.data_ptr(), dx.data_ptr() + 4 * off, dy.stride(0), dx.stride(0)
-                _lib.check(lib.agnn_relt_bwd_f32(2, items, R, heads, D, N, st), "agnn_relt_bwd_f32")
+                _relt("bwd", ((dkp[s_t], Wkt, dx[:, :H]), (dvp[s_t], Wvt, dx[:, 2 * H:])), R, heads, D, dev)
             # The relation weights' gradients only feed the optimizer: with dp.defer_weight_grads they leave the stack's backward
             # chain (95 us per layer at C3, between the input-gradient transform and the next layer's backward) and run at the
             # stream's flush.  The closure works on aliases (a second reference to the returned gradient would make
@@ -553,14 +353,9 @@ class _HGTCore(torch.autograd.Function):
                 gwk = torch.zeros(wk_shape, dtype=torch.float32, device=dev)
                 gwv = torch.zeros(wv_shape, dtype=torch.float32, device=dev)
 
-            def weight_grads(x=x, dk_=dkp[s_t], dv_=dvp[s_t], dWk=dWk.detach(), dWv=dWv.detach(), R=R, N=N, ids=ids, whole=whole,
+            def weight_grads(x=x, dk_=dkp[s_t], dv_=dvp[s_t], dWk=dWk.detach(), dWv=dWv.detach(), R=R, ids=ids, whole=whole,
                              gk=gwk.detach(), gv=gwv.detach()):
-                nws = int(lib.agnn_relt_dw_workspace_bytes(2, R, heads, D, N))
-                ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
-                items = (_lib.ReltItem * 2)()
-                for it, (off, dy, y) in zip(items, ((0, dk_, dWk), (2 * H, dv_, dWv))):
-                    it.x, it.w, it.y, it.ld_x, it.ld_y = x.data_ptr() + 4 * off, dy.data_ptr(), y.data_ptr(), x.stride(0), dy.stride(0)
-                _lib.check(lib.agnn_relt_dw_f32(2, items, R, heads, D, N, ws.data_ptr(), nws, _lib.stream_ptr(dev)), "agnn_relt_dw_f32")
+                _relt("dw", ((x[:, :H], dk_, dWk), (x[:, 2 * H:], dv_, dWv)), R, heads, D, dev)
                 if not whole:
                     sel = _index_tensor(ids, dev)
                     gk.index_copy_(0, sel, dWk)
@@ -585,14 +380,6 @@ class _HGTCore(torch.autograd.Function):
         return (None, gwk, gwv, dp_all, *[None if t in dead else dkqv[t] for t in plan.types])
 
 
-def _arange(n: int, device) -> torch.Tensor:
-    return _index_tensor(tuple(range(n)), device)
-
-
-def block_diag_weight(weight: torch.Tensor, rel_ids: tuple, n_rel: int, heads: int, D: int) -> torch.Tensor:
-    return _BlockDiagWeight.apply(weight, rel_ids, n_rel, heads, D)
-
-
 class HGTConv(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, metadata, heads: int = 1):
         super().__init__()
@@ -614,68 +401,14 @@ class HGTConv(nn.Module):
         """`post` = (relu, dropout p, training) or None: the activation the caller would apply to every output right after this
         layer (HeteroHGTStack between layers) — folded into the layer's epilogue launch; None: the plain HGTConv output."""
         _lib.require_gpu(*x_dict.values())
+        D = self.out_channels // self.heads
+        if D not in HEAD_WIDTHS or any(x.shape[1] != self.in_channels for x in x_dict.values()):
+            raise _lib.AgnnError(f"HGTConv: head width out_channels / heads = {D} must be one of {HEAD_WIDTHS}, and every input "
+                                 f"{self.in_channels} features wide (got {[tuple(x.shape) for x in x_dict.values()]})")
         if index is None:
             index = hetero_index(edge_index_dict, {k: int(v.shape[0]) for k, v in x_dict.items()})
-        heads, H = self.heads, self.out_channels
-        D = H // heads
         n_of = {t: (n_keep[t] if n_keep is not None else int(x.shape[0])) for t, x in x_dict.items()}
-        if CORE_ENABLED and RELT_ENABLED and D == RELT_D and all(x.shape[1] == self.in_channels for x in x_dict.values()):
-            return self._forward_core(x_dict, index, n_of, e_keep, post)
-        # k | q | v in ONE projection per node type; the three H-wide column blocks are handed out as views (col_split)
-        k, q, v = {}, {}, {}
-        for t, x in x_dict.items():
-            lin = self.kqv_lin.lins[t]
-            xt = x if n_of[t] >= x.shape[0] else x[:n_of[t]]
-            k[t], q[t], v[t] = col_split(linear(xt, lin.weight, lin.bias), 3)
-        by_dst: Dict[str, List[Tuple[int, EdgeType]]] = {}
-        for e_idx, et in enumerate(self.edge_types):
-            s, _, d = et
-            if et in index.fwd and s in x_dict and d in x_dict:
-                by_dst.setdefault(d, []).append((e_idx, et))
-        # Relation transforms k' = k A_r^k, v' = v A_r^v: the heads' D x D matrices of one relation are laid out as one
-        # block-diagonal [H, H] weight (one scatter for all relations), so each relation is a plain [N_s, H] x [H, H] GEMM
-        # with a well-shaped weight gradient, instead of batched 64 x 64 GEMMs whose weight gradients have K = N.
-        used = sorted({e_idx for rels in by_dst.values() for e_idx, _ in rels})
-        kv_of: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
-        if used:
-            # all relations leaving one source type share their input: ONE GEMM [N_s, H] x [H, R_s*H] for the keys and one
-            # for the values (weight gradient [R_s*H, H] in one piece), the relations' blocks handed out as column views
-            by_src: Dict[str, List[int]] = {}
-            for e_idx in used:
-                by_src.setdefault(self.edge_types[e_idx][0], []).append(e_idx)
-            for s_t, e_ids in by_src.items():
-                if RELT_ENABLED and D == RELT_D and k[s_t].is_cuda:
-                    kp, vp = _RelTransform.apply(k[s_t], v[s_t], self.k_rel.weight, self.v_rel.weight, tuple(e_ids), heads, D)
-                    ks, vs = col_split(kp, len(e_ids)), col_split(vp, len(e_ids))
-                else:
-                    Wk_s = block_diag_weight(self.k_rel.weight, tuple(e_ids), len(self.edge_types), heads, D)     # [R_s*H, H]
-                    Wv_s = block_diag_weight(self.v_rel.weight, tuple(e_ids), len(self.edge_types), heads, D)
-                    ks = col_split(linear(k[s_t], Wk_s), len(e_ids))
-                    vs = col_split(linear(v[s_t], Wv_s), len(e_ids))
-                for j, e_idx in enumerate(e_ids):
-                    kv_of[e_idx] = (ks[j], vs[j])
-        out = {}
-        for t, x in x_dict.items():
-            n = n_of[t]
-            rels = by_dst.get(t, [])
-            if rels and n > 0:
-                kv, ps = [], []
-                for e_idx, et in rels:
-                    kv += list(kv_of[e_idx])
-                    ps.append(self.p_rel["__".join(et)].reshape(heads) / math.sqrt(D))
-                spec = _AttnSpec(fwd=[index.fwd[et] for _, et in rels], bwd=[index.bwd[et] for _, et in rels], n_rows=n,
-                                 heads=heads, n_edges=[index.num_edges[et] for _, et in rels],
-                                 e_limit=[e_keep[et] for _, et in rels] if e_keep is not None else None,
-                                 src_rows=[kv[2 * i].shape[0] for i in range(len(rels))])
-                m = _HGTAttention.apply(spec, q[t], torch.stack(ps), *kv)
-            else:
-                m = x.new_zeros((n, H))
-            o = self.out_lin.lins[t](F.gelu(m))
-            relu, p, training = post if post is not None else (False, 0.0, False)
-            xs = (x if n >= x.shape[0] else x[:n]) if o.shape[-1] == x.shape[-1] else None
-            out[t] = skip_act(o, xs, self.skip[t] if xs is not None else None, relu, p, training)
-        return out
-
+        return self._forward_core(x_dict, index, n_of, e_keep, post)
 
     def adjacent_parameter_groups(self):
         """The per-relation priors are consumed stacked (one [n_edge_types, heads] operand): adjacent in the flat buffer
@@ -806,10 +539,14 @@ def attention_roofline_case(g, I, hid: int, dev, timed, hbm_peak: float, heads: 
     for et in ets:
         kv += [torch.randn(n_nodes[et[0]], hid, generator=gen).to(dev), torch.randn(n_nodes[et[0]], hid, generator=gen).to(dev)]
     ps = torch.full((len(ets), heads), 1.0 / math.sqrt(hid // heads), device=dev)
-    spec = _AttnSpec(fwd=[hix.fwd[et] for et in ets], bwd=[hix.bwd[et] for et in ets], n_rows=n, heads=heads,
-                     n_edges=[hix.num_edges[et] for et in ets], e_limit=None, src_rows=[n_nodes[et[0]] for et in ets])
-    with torch.no_grad():
-        t_k, launches = timed(lambda: _HGTAttention.apply(spec, q, ps, *kv))
+    rels = (_lib.HgtRel * len(ets))()
+    for r, et in enumerate(ets):
+        c, k, v = hix.fwd[et], kv[2 * r], kv[2 * r + 1]
+        rels[r].k, rels[r].v, rels[r].ld, rels[r].pscale = k.data_ptr(), v.data_ptr(), k.stride(0), ps[r].data_ptr()
+        rels[r].rowptr, rels[r].col, rels[r].perm = c.rowptr.data_ptr(), c.col.data_ptr(), c.perm.data_ptr()
+    out = torch.empty((n, hid), device=dev)
+    m, linv = torch.empty((n, heads), device=dev), torch.empty((n, heads), device=dev)
+    t_k, launches = timed(lambda: attention_forward(rels, q, out, m, linv, heads))
     b_alg, e_tot = 0, 0
     for et in ets:
         ei = g.edge_index[et]

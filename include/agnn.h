@@ -212,7 +212,7 @@ int agnn_gru_hprev_f32(const float* y, int64_t B, int64_t T, int32_t hidden, flo
  * For destination row i, head h (D = H / heads floats per head), over ALL incoming edges e of all
  * n_rel relations:   s_e = <q_i,h, k_r[col_e],h> * pscale_r[h]      (pscale = p_rel / sqrt(D))
  *                    a_e = exp(s_e - max) / (sum exp(s_e - max) + 1e-16),   out_i,h = sum_e a_e v_r[col_e],h
- * k_r / v_r are the relation-transformed keys / values of the source type (dense GEMMs by the caller).
+ * k_r / v_r are the relation-transformed keys / values of the source type (computed by the caller).
  * m_out / linv_out [n_rows, heads] keep the row max and 1/(sum + 1e-16) for the backward pass.
  * D must be 4*2^k, <= 256.
  * Backward, pass by destination: dq plus per-edge alpha, gs = ds*pscale, tdot = ds*<q,k> written at the
@@ -259,13 +259,9 @@ int agnn_hgt_attn_bwd_dst_f32(int n_rel, const agnn_hgt_rel_t* rels /* (host) */
                               const float* dm, int64_t ld_dm, const float* out, int64_t ld_out,
                               const float* m_in, const float* linv_in, int64_t n_rows, int32_t H,
                               int32_t heads, float* dq, int64_t ld_dq, agnn_stream_t stream);
-int agnn_hgt_attn_bwd_src_f32(const int32_t* rowptr, const int32_t* rowend, const int32_t* col,
-                              const int32_t* perm, const float* alpha, const float* gs, const float* q,
-                              int64_t ld_q, const float* dm, int64_t ld_dm, int64_t n_src_rows,
-                              int32_t col_limit, int32_t H, int32_t heads, float* dk, float* dv,
-                              int64_t ld_o, agnn_stream_t stream);
-/* The same for up to AGNN_MAX_SEG relations in one launch — all relations ending in one destination type share q and dm; item i
- * writes its own dk / dv (a column block of its source type's gradient).  Items are read on the host during the call. */
+/* Backward, pass by source, for up to AGNN_MAX_SEG relations in one launch (item i = one relation) — all relations ending in one
+ * destination type share q and dm; item i writes its own dk / dv (a column block of its source type's gradient).  Items are read
+ * on the host during the call. */
 typedef struct {
   const int32_t* rowptr;
   const int32_t* rowend;      /* NULL: rowptr + 1 */

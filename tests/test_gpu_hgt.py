@@ -84,11 +84,12 @@ def test_hgt_conv_layer(kind, C, heads):
     _cmp_grads(m, P)
 
 
-def test_attention_weights_sum_to_one():
+def test_attention_forward_weights_sum_to_one():
     """Property at the C3 shape (H=256, heads=4, 32 x 500 notes + beats + measures): with v' = 1 every destination
     row that has an incoming edge aggregates exactly 1 (sum of softmax weights), rows without edges give 0."""
+    from analysisgnn_amd import _lib
     from analysisgnn_amd.graph import HeteroIndex
-    from analysisgnn_amd.hgt import _AttnSpec, _HGTAttention
+    from analysisgnn_amd.hgt import attention_forward
     from analysisgnn_amd.synth import make_batch
     g = make_batch(32, 500, add_beats=True, add_measures=True)
     ets = [et for et in g.edge_types if et[0] == "note" and et[2] == "beat"] + []
@@ -103,10 +104,15 @@ def test_attention_weights_sum_to_one():
         kv = []
         for et in rels:
             kv += [torch.randn(g.num_nodes[et[0]], 256, generator=gen).to(dev), torch.ones(g.num_nodes[et[0]], 256, device=dev)]
-        spec = _AttnSpec([hix.fwd[e] for e in rels], [hix.bwd[e] for e in rels], n, 4, [hix.num_edges[e] for e in rels], None,
-                         [g.num_nodes[e[0]] for e in rels])
         ps = torch.rand(len(rels), 4, generator=gen).to(dev) + 0.5
-        out = _HGTAttention.apply(spec, q, ps, *kv)
+        table = (_lib.HgtRel * len(rels))()
+        for r, et in enumerate(rels):
+            c = hix.fwd[et]
+            table[r].k, table[r].v, table[r].ld, table[r].pscale = kv[2 * r].data_ptr(), kv[2 * r + 1].data_ptr(), 256, ps[r].data_ptr()
+            table[r].rowptr, table[r].col, table[r].perm = c.rowptr.data_ptr(), c.col.data_ptr(), c.perm.data_ptr()
+        out = torch.empty(n, 256, device=dev)
+        m, linv = torch.empty(n, 4, device=dev), torch.empty(n, 4, device=dev)
+        attention_forward(table, q, out, m, linv, 4)
         deg = torch.zeros(n, device=dev)
         for et in rels:
             deg.index_add_(0, eid[et][1], torch.ones(eid[et].shape[1], device=dev))
@@ -168,13 +174,16 @@ def test_analysis_model_hgt_logits():
         assert_close(out[t], ref[t], TOL, f"logits[{t}]")
 
 
-@pytest.mark.parametrize("N,R,heads,T", [(16000, 6, 4, 6), (1003, 2, 4, 7), (130, 1, 1, 3), (5, 3, 2, 3)])
-def test_relation_transform_kernels_match_float64(N, R, heads, T):
-    """agnn_relt_fwd / _bwd / _dw (the per-head D x D relation transforms of HGTConv, D = 64) against per-block float64
-    matmuls: K and V in one launch, relations picked out of a larger parameter (`rel_ids`), rows not a multiple of the
-    128-row tile, gradients w.r.t. both operands and both parameters."""
-    from analysisgnn_amd.hgt import _RelTransform
-    D, H = 64, heads * 64
+@pytest.mark.parametrize("N,R,heads,T,D", [(16000, 6, 4, 6, 64), (1003, 2, 4, 7, 64), (130, 1, 1, 3, 64), (5, 3, 2, 3, 64),
+                                           (1003, 2, 4, 7, 8), (1003, 2, 4, 7, 16)])
+def test_relation_transforms_match_float64(N, R, heads, T, D):
+    """The per-head D x D relation transforms of HGTConv as `_HGTCore` issues them (hgt._relt: agnn_relt_fwd / _bwd / _dw at
+    D = 64, torch batched matmuls at other head widths) against per-block float64 matmuls: K and V in one call, relations picked
+    out of a larger parameter (`rel_ids`), rows not a multiple of the 128-row tile, gradients w.r.t. both operands and both
+    parameters."""
+    from analysisgnn_amd.hgt import _relt
+    H = heads * D
+    dev = torch.device(DEV)
     g = torch.Generator().manual_seed(N + R)
     rel_ids = tuple(sorted(torch.randperm(T, generator=g)[:R].tolist()))
     kqv = torch.randn(N, 3 * H, generator=g)                       # K | Q | V side by side: the operands are column views
@@ -191,15 +200,21 @@ def test_relation_transform_kernels_match_float64(N, R, heads, T):
         return torch.cat(blocks, dim=1)
     rk, rv = ref_of(kqv64[:, :H], wk64), ref_of(kqv64[:, 2 * H:], wv64)
     ((rk * gk.double()).sum() + (rv * gv.double()).sum()).backward()
-    kd = kqv.to(DEV).requires_grad_(True)
-    wkd, wvd = wk.to(DEV).requires_grad_(True), wv.to(DEV).requires_grad_(True)
-    yk, yv = _RelTransform.apply(kd[:, :H], kd[:, 2 * H:], wkd, wvd, rel_ids, heads, D)
-    ((yk * gk.to(DEV)).sum() + (yv * gv.to(DEV)).sum()).backward()
+    kd, wkd, wvd, gkd, gvd = (t.to(dev) for t in (kqv, wk, wv, gk, gv))
+    sel = torch.tensor([r * heads + h for r in rel_ids for h in range(heads)], device=dev)
+    Wk, Wv = wkd.index_select(0, sel), wvd.index_select(0, sel)
+    yk, yv = torch.empty(N, R * H, device=dev), torch.empty(N, R * H, device=dev)
+    _relt("fwd", ((kd[:, :H], Wk, yk), (kd[:, 2 * H:], Wv, yv)), R, heads, D, dev)
+    dkqv = torch.zeros(N, 3 * H, device=dev)                        # the gradients of the K and V column views; Q's stays 0
+    _relt("bwd", ((gkd, Wk.transpose(1, 2).contiguous(), dkqv[:, :H]), (gvd, Wv.transpose(1, 2).contiguous(), dkqv[:, 2 * H:])),
+          R, heads, D, dev)
+    dWk, dWv = torch.empty_like(Wk), torch.empty_like(Wv)
+    _relt("dw", ((kd[:, :H], gkd, dWk), (kd[:, 2 * H:], gvd, dWv)), R, heads, D, dev)
     assert_close(yk, rk.float(), 1e-5, "k'")
     assert_close(yv, rv.float(), 1e-5, "v'")
-    assert_close(kd.grad, kqv64.grad.float(), 1e-5, "d kqv")
-    assert_close(wkd.grad, wk64.grad.float(), 1e-5, "d k_rel.weight")
-    assert_close(wvd.grad, wv64.grad.float(), 1e-5, "d v_rel.weight")
+    assert_close(dkqv, kqv64.grad.float(), 1e-5, "d kqv")
+    assert_close(torch.zeros_like(wkd).index_copy_(0, sel, dWk), wk64.grad.float(), 1e-5, "d k_rel.weight")
+    assert_close(torch.zeros_like(wvd).index_copy_(0, sel, dWv), wv64.grad.float(), 1e-5, "d v_rel.weight")
 
 
 @pytest.mark.parametrize("n,H,relu,p,with_x", [(16000, 256, True, 0.0, True), (3584, 256, True, 0.3, True), (897, 64, False, 0.0, True),
