@@ -76,7 +76,10 @@ def trim_to_layer(layer: int, nodes_per_hop, edges_per_hop, x_dict, ei_dict):
 
 # A.4  HGTConv (PyG >= 2.3)
 def hgt_conv(P: Params, pre: str, node_types: Sequence[str], edge_types: Sequence[EdgeType], heads: int,
-             x_dict, ei_dict):
+             x_dict, ei_dict, taps: Optional[dict] = None):
+    """`taps` (a dict, filled when given; the result is the same either way) receives the layer's MESSAGE stage as the
+    attention sees it: taps["q"][t] [n_t, out], taps["rels"][t] = [(edge type, k' [n_s, out], v' [n_s, out], pscale [heads])]
+    for the relations that end in t, and taps["m"][t] [n_t, out], the aggregated messages the epilogue starts from."""
     any_x = next(iter(x_dict.values()))
     out_ch = P[f"{pre}out_lin.lins.{node_types[0]}.weight"].shape[0]
     D = out_ch // heads
@@ -100,6 +103,9 @@ def hgt_conv(P: Params, pre: str, node_types: Sequence[str], edge_types: Sequenc
         p = P[f"{pre}p_rel.{'__'.join(et)}"].view(1, heads)
         logit = (q_d[d][ei[1]] * k2[ei[0]]).sum(-1) * p / math.sqrt(D)          # [E, heads]
         msgs[d].append((ei[1], logit, v2[ei[0]]))
+        if taps is not None:
+            taps.setdefault("rels", {}).setdefault(d, []).append((et, k2.reshape(-1, out_ch), v2.reshape(-1, out_ch),
+                                                                   p.reshape(heads) / math.sqrt(D)))
     out_dict = {}
     for t in x_dict:
         n = n_dst[t]
@@ -116,6 +122,9 @@ def hgt_conv(P: Params, pre: str, node_types: Sequence[str], edge_types: Sequenc
             m = m.reshape(n, out_ch)
         else:
             m = any_x.new_zeros(n, out_ch)
+        if taps is not None:
+            taps.setdefault("q", {})[t] = q_d[t].reshape(n, out_ch)
+            taps.setdefault("m", {})[t] = m
         o = F.gelu(m) @ P[f"{pre}out_lin.lins.{t}.weight"].t() + P[f"{pre}out_lin.lins.{t}.bias"]
         if o.shape[-1] == x_dict[t].shape[-1]:
             beta = torch.sigmoid(P[f"{pre}skip.{t}"])

@@ -99,6 +99,28 @@ def test_rows_with_more_than_64_neighbours_h256():
             else:
                 ref = G.hgt_conv(P, "", ["note"], g.edge_types, 4, I["x_dict"], I["edge_index_dict"])
         assert_close(out["note"], ref["note"], 1e-4, type(m).__name__)
+    # the HGT layer once more with gradients — the only layer-level case in which the attention's backward passes (by
+    # destination and by source) meet rows of more than 64 edges: input and parameter gradients against autograd through the
+    # restatement, each relative to its own largest magnitude
+    from helpers import assert_close_rel
+    Pg = {k: v.clone().requires_grad_(v.is_floating_point()) for k, v in P.items()}
+    xc = {k: v.clone().requires_grad_(True) for k, v in I["x_dict"].items()}
+    ref = G.hgt_conv(Pg, "", ["note"], g.edge_types, 4, xc, I["edge_index_dict"])["note"]
+    xg = {k: v.to(DEV).requires_grad_(True) for k, v in I["x_dict"].items()}
+    out = m(xg, {k: v.to(DEV) for k, v in I["edge_index_dict"].items()})["note"]
+    go = torch.randn(ref.shape, generator=torch.Generator().manual_seed(2))
+    (ref * go).sum().backward()
+    (out * go.to(DEV)).sum().backward()
+    assert_close_rel(xg["note"].grad, xc["note"].grad, 1e-4, "HGTConv d x[note]")
+    n_par = 0
+    for name, p in m.named_parameters():
+        if Pg[name].grad is None:
+            assert p.grad is None or float(p.grad.abs().max()) == 0.0, name
+            continue
+        assert p.grad is not None, f"{name}: no gradient on the HIP path"
+        assert_close_rel(p.grad, Pg[name].grad, 1e-4, f"HGTConv grad {name}")
+        n_par += 1
+    assert n_par >= 8
 
 
 def test_empty_batch_kernels_do_not_launch():

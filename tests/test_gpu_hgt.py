@@ -47,8 +47,10 @@ def _c3_edge_types(g):
     return [et for et in g.edge_types if et[0] == "note"]
 
 
-@pytest.mark.parametrize("kind", ["notes", "c3", "metrical_rev"])
-@pytest.mark.parametrize("C,heads", [(32, 4), (64, 1), (256, 4)])
+# every graph at D = 8 and 64; the ends of the head-width range (D = 4, 128, 256 — the last at H = 512, two chunks per row) on the
+# C3 graph: the relation transforms' torch path and the RELT_D dispatch of `_relt` beside the attention kernels
+@pytest.mark.parametrize("C,heads,kind", [(C, heads, kind) for C, heads in [(32, 4), (64, 1), (256, 4)] for kind in ["notes", "c3", "metrical_rev"]]
+                         + [(64, 16, "c3"), (128, 1, "c3"), (512, 2, "c3")])
 def test_hgt_conv_layer(kind, C, heads):
     from analysisgnn_amd.hgt import HGTConv
     from analysisgnn_amd.synth import torch_inputs
