@@ -3,24 +3,53 @@
 //     k'[n, r, h, :] = k[n, h, :] @ A[r, h]          for every relation r leaving the node type, every head h
 // Round 1 ran them as ONE dense library GEMM against a block-diagonal [H, R*H] weight: 4x the useful FLOPs at heads = 4
 // (12.6 GFLOP instead of 3.1 per operand and layer at the C3 shape) plus the launches that assemble the weight.
-// Here they are what they are: R*heads independent [N, D] x [D, D] products on the fp32-input MFMA
-// (v_mfma_f32_32x32x2_f32: exact fp32, 64 FLOP/clk/SIMD), D = 64.
+// Here they are what they are: R*heads independent [N, D] x [D, D] products, at every head width the attention kernels
+// take (D = 4, 8, 16, 32, 64, 128, 256).  Per item the work is 2 N R H D FLOP over 4 N H (1 + R) + 4 R heads D^2 bytes,
+// ~D/2 FLOP per byte against a ridge of ~25 (fp32 MFMA over HBM): D <= 32 is byte-bound, D = 64 sits at the ridge,
+// D >= 128 is MFMA-bound — three kernel families, not one template stretched over the range.
+//
+// D = 64 (v_mfma_f32_32x32x2_f32: exact fp32, 64 FLOP/clk/SIMD):
 //   k_relt<false>  forward: one workgroup = 128 rows x one head; a wave keeps its 32 x 64 slice of k in registers (the A
 //                  operand of all R products) and walks the relations; A[r, h] (16 KB) is staged through LDS, double
 //                  buffered, once per workgroup; the 32 x 64 result of every relation is written as whole 128-byte lines.
 //   k_relt<true>   input gradient: dk[n, h, :] = sum_r dk'[n, r, h, :] @ A[r, h]^T — the same loop with the roles
 //                  swapped (the A operand changes per relation, ONE accumulator is carried across the relations); the
 //                  caller passes the transposed blocks.
-//   k_relt_dw      weight gradient: dA[r, h] = k[:, h, :]^T dk'[:, r, h, :], a 64 x 64 output with the reduction over N:
+//   k_relt_dw<64>  weight gradient: dA[r, h] = k[:, h, :]^T dk'[:, r, h, :], a 64 x 64 output with the reduction over N:
 //                  one wave = one (relation, head, row slice), operands straight from global memory (already "k-major":
 //                  one MFMA k-step = two consecutive rows, as in wgrad.hip), slices summed in a fixed order by
 //                  agnn::launch_slab_reduce (no atomics).
+// D = 128, 256 (the same instruction, the same pipeline, tiled over D):
+//   k_relt_wide    a D x D block no longer fits the LDS (256 KB at D = 256), so the unit of work is one 64 x 64 piece of it:
+//                  k-chunk kc x column tile ct.  A workgroup owns 128 rows, one head and ONE column tile (blockIdx.x walks
+//                  the column tiles fastest, so the workgroups that share rows run together) and walks (relation, k-chunk);
+//                  the 16 KB pieces go through the two LDS buffers exactly as A[r, h] does at D = 64, the wave's 32 x D
+//                  row slice sits in registers as D/64 chunks.  Forward: the accumulator pair restarts with every
+//                  relation and is stored after its last k-chunk; input gradient: it is carried to the end, and chunk kc
+//                  of the next relation's dk' is loaded right behind the MFMAs that consumed chunk kc of this one.
+//   k_relt_dw<D>   the D = 64 kernel, one wave per 64 x 64 TILE of dA[r, h]: (D/64)^2 tiles per (relation, head).
+// D = 16, 32 (byte-bound; one MFMA tile IS the block: v_mfma_f32_16x16x4_f32 at D = 16, v_mfma_f32_32x32x2_f32 at D = 32 —
+// no zero padding, no multiplied FLOPs; the multi-block forms would only pay with several heads per wave, which the
+// item layout does not give: a head's block is D columns of a row, the next head's the next D):
+//   k_relt_tile    one wave = D rows x one head (D/4 inputs of its row per lane: 16-byte loads), all relations' blocks of
+//                  the head staged in LDS in passes of 8; D/(64/D) MFMAs per relation; input gradient with the next
+//                  relation's operand loaded ahead.
+//   k_relt_dw_tile one wave = one (relation, head, row slice), one accumulator tile, three register stages of loads.
+// D = 4, 8 (a block is 64 or 256 bytes: plain VALU FMAs; even the smallest MFMA tile would be mostly zeros):
+//   k_relt_valu    one thread = one output element; its D inputs in registers, the blocks of a pass of relations in LDS
+//                  (consecutive lanes read consecutive words), D FMAs, consecutive lanes store consecutive words.
+//   k_relt_dw_valu one thread = one ROW of a block gradient (D accumulators) over a row slice, rows in groups of 8 loads.
+// Weight gradient slices (relt_dw_plan): S = min(S_max, ceil(N / rows_min)) row slices, rows per slice rounded up to a
+// multiple of 4 (of 2 at D = 64, as ever), with (rows_min, S_max) = (64, 256) at D <= 8, (256, 64) at D = 16 / 32, (512, 32) at D = 64, (512, 8) at
+// D = 128, (512, 2) at D = 256 (the slab of one slice grows with D^2, the tiles per (relation, head) with (D/64)^2).
+// Workspace = n_items * S * n_rel * heads * D * D * 4 + 256 bytes (agnn_relt_dw_workspace_bytes is the authority).
 // K and V (and anything else that shares the shape) go through ONE launch: up to 4 items per call.
 #include "agnn_common.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kD = 64;
 
@@ -173,9 +202,13 @@ __global__ __launch_bounds__(256) void k_relt(ReltArgs p) {
 // and of dy per workgroup); a wave's 64 x 64 output is four 32 x 32 accumulators; a lane loads TWO adjacent columns of
 // both operands per row (8 bytes: columns 2*c32, 2*c32 + 1 feed the two tiles of that operand), the lane halves take the
 // two rows of a k-step.  Three register stages in rotation (two chunks of loads in flight), as in wgrad.hip.
+// D = 128, 256: a wave takes one 64 x 64 tile (ti, tj) of the D x D output, the four waves of a workgroup four consecutive
+// (head, tile) jobs: at D = 128 the four tiles of one head, which share their two x and two dy pieces.
+template <int D>
 __global__ __launch_bounds__(256) void k_relt_dw(ReltArgs p) {
-  constexpr int D = kD;
-  const int lane = threadIdx.x & 63, h = blockIdx.z * 4 + (threadIdx.x >> 6);      // up to four heads per workgroup
+  constexpr int NT = D / 64;
+  const int lane = threadIdx.x & 63, job = blockIdx.z * 4 + (threadIdx.x >> 6);    // up to four (head, tile) jobs per workgroup
+  const int h = job / (NT * NT), ti = (job / NT) % NT, tj = job % NT;
   if (h >= p.heads) return;
   const int c32 = lane & 31, kk = lane >> 5;
   const int item = blockIdx.x / p.n_rel, r = blockIdx.x - item * p.n_rel;
@@ -187,8 +220,8 @@ __global__ __launch_bounds__(256) void k_relt_dw(ReltArgs p) {
   if (r1 > p.n_rows) r1 = p.n_rows;
   f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
   if (r0 < r1) {
-    const float* xs = I.x + h * D + 2 * c32;              // operand "A": rows of the 64 x 64 output = input feature i
-    const float* ys = I.w + rh * D + 2 * c32;             // operand "B": columns = output feature j
+    const float* xs = I.x + h * D + ti * 64 + 2 * c32;    // operand "A": rows of the 64 x 64 output = input feature i
+    const float* ys = I.w + rh * D + tj * 64 + 2 * c32;   // operand "B": columns = output feature j
     constexpr int CH = 8;
     constexpr int STEP = 2 * CH;
     float2 a0[CH], b0[CH], a1[CH], b1[CH], a2[CH], b2[CH];
@@ -245,19 +278,408 @@ __global__ __launch_bounds__(256) void k_relt_dw(ReltArgs p) {
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
     const int i = (q & 3) + 8 * (q >> 2) + 4 * kk;
-    float* o = slab + (2 * i) * D + 2 * c32;
+    float* o = slab + (ti * 64 + 2 * i) * D + tj * 64 + 2 * c32;
     *reinterpret_cast<float2*>(o) = make_float2(acc00[q], acc01[q]);
     *reinterpret_cast<float2*>(o + D) = make_float2(acc10[q], acc11[q]);
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// D = 128, 256: forward and input gradient.  Everything inside a unit (one 64 x 64 piece of the block: rows kc*64 .. of it,
+// columns ct*64 ..) is k_relt's relation: the lessons written there hold here (named staging registers, the A operand waited
+// for outside the loop where it is loop-invariant, LDS reads a chunk ahead of the MFMAs).  NC = D/64 is even, so the LDS buffer
+// of unit (r, kc) is kc & 1 and the k-chunk loop unrolls with every register array indexed by a constant.
+template <int D, bool BWD>
+__global__ __launch_bounds__(256) void k_relt_wide(ReltArgs p) {
+  constexpr int NC = D / 64;
+  static_assert(NC >= 2 && NC % 2 == 0, "the LDS buffer parity relies on an even chunk count");
+  __shared__ __attribute__((aligned(16))) float sW[2][64 * 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c32 = lane & 31, kk = lane >> 5;
+  const int ct = blockIdx.x % NC;
+  const int h = blockIdx.y % p.heads, item = blockIdx.y / p.heads;
+  const ReltItem& I = p.it[item];
+  const int64_t row0 = static_cast<int64_t>(blockIdx.x / NC) * 128 + wave * 32;
+  int64_t rowc = row0 + c32;
+  if (rowc > p.n_rows - 1) rowc = p.n_rows - 1;
+
+  float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = w0, w2 = w0, w3 = w0;
+  const float* const wsrc = I.w + (tid >> 4) * D + ct * 64 + (tid & 15) * 4;      // this thread's 16 bytes of rows tid/16 + 16 j
+  auto fetch_w = [&](int r, int kc) {
+    const float* src = wsrc + (static_cast<size_t>(r * p.heads + h) * D + kc * 64) * D;
+    w0 = *reinterpret_cast<const float4*>(src);
+    w1 = *reinterpret_cast<const float4*>(src + 16 * D);
+    w2 = *reinterpret_cast<const float4*>(src + 32 * D);
+    w3 = *reinterpret_cast<const float4*>(src + 48 * D);
+  };
+  auto put_w = [&](int buf) {
+    float4* dst = reinterpret_cast<float4*>(sW[buf]) + tid;
+    dst[0] = w0;
+    dst[256] = w1;
+    dst[512] = w2;
+    dst[768] = w3;
+  };
+  const float* xrow = I.x + rowc * I.ld_x + kk * 32;
+  auto load_a = [&](float4 (&dst)[8], int colbase) {
+    const float4* src = reinterpret_cast<const float4*>(xrow + colbase);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) dst[u] = src[u];
+  };
+  const bool full = row0 + 32 <= p.n_rows;
+  float* const ybase = I.y + (row0 + 4 * kk) * I.ld_y + c32;
+  auto store = [&](const f32x16& acc0, const f32x16& acc1, int colbase) {
+    float* o = ybase + colbase;
+    if (full) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        float* oq = o + ((q & 3) + 8 * (q >> 2)) * I.ld_y;
+        oq[0] = acc0[q];
+        oq[32] = acc1[q];
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        if (row0 + (q & 3) + 8 * (q >> 2) + 4 * kk < p.n_rows) {
+          float* oq = o + ((q & 3) + 8 * (q >> 2)) * I.ld_y;
+          oq[0] = acc0[q];
+          oq[32] = acc1[q];
+        }
+      }
+    }
+  };
+  auto product = [&](const float4 (&av)[8], int buf, f32x16& acc0, f32x16& acc1) {
+    const float* sw = sW[buf] + kk * 32 * 64 + c32;
+    float b0[2][8], b1[2][8];
+    auto rd = [&](int c, int slot) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        b0[slot][u] = sw[(8 * c + u) * 64];
+        b1[slot][u] = sw[(8 * c + u) * 64 + 32];
+      }
+    };
+    rd(0, 0);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (c + 1 < 4) rd(c + 1, (c + 1) & 1);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const float4 q = av[2 * c + (u >> 2)];
+        const float as = (u & 3) == 0 ? q.x : (u & 3) == 1 ? q.y : (u & 3) == 2 ? q.z : q.w;
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(as, b0[c & 1][u], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(as, b1[c & 1][u], acc1, 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  fetch_w(0, 0);
+  put_w(0);
+  float4 a[NC][8];                                       // the wave's 32 x D row slice (BWD: of the current relation's dy block)
+#pragma unroll
+  for (int kc = 0; kc < NC; ++kc) load_a(a[kc], h * D + kc * 64);
+  if (!BWD) {
+#pragma unroll
+    for (int kc = 0; kc < NC; ++kc)
+#pragma unroll
+      for (int u = 0; u < 8; ++u) asm volatile("" ::"v"(a[kc][u].x), "v"(a[kc][u].y), "v"(a[kc][u].z), "v"(a[kc][u].w));
+  }
+  f32x16 acc0 = {0}, acc1 = {0};
+  __syncthreads();
+  for (int r = 0; r < p.n_rel; ++r) {
+    const bool more = r + 1 < p.n_rel;
+#pragma unroll
+    for (int kc = 0; kc < NC; ++kc) {
+      constexpr int kLast = NC - 1;
+      if (kc < kLast) fetch_w(r, kc + 1);
+      else if (more) fetch_w(r + 1, 0);
+      if (!BWD && kc == 0) {
+        acc0 = f32x16{0};
+        acc1 = f32x16{0};
+      }
+      product(a[kc], kc & 1, acc0, acc1);
+      if (BWD && more) load_a(a[kc], ((r + 1) * p.heads + h) * D + kc * 64);
+      if (!BWD && kc == kLast) store(acc0, acc1, (r * p.heads + h) * D + ct * 64);
+      if (kc < kLast || more) put_w((kc + 1) & 1);       // that buffer was last read in the previous unit (barrier below)
+      __syncthreads();
+    }
+  }
+  if (BWD) store(acc0, acc1, h * D + ct * 64);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// D = 16, 32: the block is one MFMA tile.  T = D; 64/T lane groups share a tile row, each holds T/(64/T) consecutive
+// inputs of its row (the k order inside a product is free as long as both operands use the same one).
+template <int T> struct TileMfma;
+template <> struct TileMfma<32> {
+  typedef f32x16 acc_t;
+  static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+};
+template <> struct TileMfma<16> {
+  typedef f32x4 acc_t;
+  static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+};
+
+template <int T, bool BWD>
+__global__ __launch_bounds__(256) void k_relt_tile(ReltArgs p) {
+  constexpr int KL = 64 / T;                             // lane groups = inputs per MFMA step (2 / 4)
+  constexpr int KS = T / KL;                             // MFMA steps per product = inputs per lane (16 / 4)
+  constexpr int NQ = T * T / 64;                         // accumulator registers (16 / 4)
+  constexpr int RC = 8;                                  // relations staged per pass
+  typedef typename TileMfma<T>::acc_t acc_t;
+  __shared__ __attribute__((aligned(16))) float sW[RC * T * T];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane % T, kk = lane / T;
+  const int h = blockIdx.y % p.heads, item = blockIdx.y / p.heads;
+  const ReltItem& I = p.it[item];
+  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * (4 * T) + wave * T;
+  int64_t rowc = row0 + c;
+  if (rowc > p.n_rows - 1) rowc = p.n_rows - 1;
+  const float* xrow = I.x + rowc * I.ld_x + kk * KS;
+  auto load_a = [&](float4 (&dst)[KS / 4], int colbase) {
+    const float4* src = reinterpret_cast<const float4*>(xrow + colbase);
+#pragma unroll
+    for (int u = 0; u < KS / 4; ++u) dst[u] = src[u];
+  };
+  // C/D layout of both MFMAs: lane l, register q -> row (q&3) + 4*KL*(q>>2) + 4*(l/T), column l % T
+  float* const ybase = I.y + (row0 + 4 * kk) * I.ld_y + c;
+  auto store = [&](const acc_t& acc, int colbase) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int rq = (q & 3) + 4 * KL * (q >> 2);
+      if (row0 + rq + 4 * kk < p.n_rows) ybase[rq * I.ld_y + colbase] = acc[q];
+    }
+  };
+  float4 cur[KS / 4], nxt[KS / 4];
+  load_a(cur, h * T);                                    // BWD: relation 0's block is (0*heads + h)*T = h*T as well
+  acc_t acc = {0};
+  for (int r0 = 0; r0 < p.n_rel; r0 += RC) {
+    const int nr = p.n_rel - r0 < RC ? p.n_rel - r0 : RC;
+    __syncthreads();                                     // the previous pass has been read
+    for (int rr = 0; rr < nr; ++rr) {
+      const float4* src = reinterpret_cast<const float4*>(I.w + static_cast<size_t>((r0 + rr) * p.heads + h) * T * T);
+      float4* dst = reinterpret_cast<float4*>(sW + rr * T * T);
+      for (int i = tid; i < T * T / 4; i += 256) dst[i] = src[i];
+    }
+    __syncthreads();
+    for (int rr = 0; rr < nr; ++rr) {
+      const int r = r0 + rr;
+      if (BWD && r + 1 < p.n_rel) load_a(nxt, ((r + 1) * p.heads + h) * T);
+      if (!BWD) acc = acc_t{0};
+      const float* sw = sW + rr * T * T + kk * KS * T + c;
+#pragma unroll
+      for (int u = 0; u < KS; ++u) {
+        const float4 q = cur[u >> 2];
+        const float as = (u & 3) == 0 ? q.x : (u & 3) == 1 ? q.y : (u & 3) == 2 ? q.z : q.w;
+        acc = TileMfma<T>::mma(as, sw[u * T], acc);
+      }
+      if (!BWD) store(acc, (r * p.heads + h) * T);
+      if (BWD && r + 1 < p.n_rel) {
+#pragma unroll
+        for (int u = 0; u < KS / 4; ++u) cur[u] = nxt[u];
+      }
+    }
+  }
+  if (BWD) store(acc, h * T);
+}
+
+// dA[r, h] (T x T) = x[:, h, :]^T dy[:, r, h, :]: one wave = (item, relation, row slice, head), the heads of a workgroup read
+// adjacent pieces of the same rows; one MFMA k-step = 64/T consecutive rows; three register stages in rotation as in k_relt_dw.
+template <int T>
+__global__ __launch_bounds__(256) void k_relt_dw_tile(ReltArgs p) {
+  constexpr int KL = 64 / T, NQ = T * T / 64;
+  typedef typename TileMfma<T>::acc_t acc_t;
+  const int lane = threadIdx.x & 63, h = blockIdx.z * 4 + (threadIdx.x >> 6);
+  if (h >= p.heads) return;
+  const int c = lane % T, kk = lane / T;
+  const int item = blockIdx.x / p.n_rel, r = blockIdx.x - item * p.n_rel;
+  const int rh = r * p.heads + h;
+  const ReltItem& I = p.it[item];
+  const int slice = blockIdx.y;
+  const int64_t r0 = static_cast<int64_t>(slice) * p.rows_per_slice;
+  int64_t r1 = r0 + p.rows_per_slice;
+  if (r1 > p.n_rows) r1 = p.n_rows;
+  acc_t acc = {0};
+  if (r0 < r1) {
+    const float* xs = I.x + h * T + c;
+    const float* ys = I.w + rh * T + c;
+    constexpr int CH = 8;
+    constexpr int STEP = KL * CH;
+    float a0[CH], b0[CH], a1[CH], b1[CH], a2[CH], b2[CH];
+    auto fetch = [&](int64_t base, float* ao, float* bo) {
+#pragma unroll
+      for (int u = 0; u < CH; ++u) {
+        int64_t row = base + KL * u + kk;
+        if (row > p.n_rows - 1) row = p.n_rows - 1;
+        ao[u] = xs[row * I.ld_x];
+        bo[u] = ys[row * I.ld_y];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    auto mma = [&](const float* ao, const float* bo) {
+#pragma unroll
+      for (int u = 0; u < CH; ++u) acc = TileMfma<T>::mma(ao[u], bo[u], acc);
+    };
+    auto mma_tail = [&](int64_t base, const float* ao, const float* bo) {       // rows >= r1 contribute nothing
+#pragma unroll
+      for (int u = 0; u < CH; ++u) {
+        const float m = (base + KL * u + kk < r1) ? 1.f : 0.f;
+        acc = TileMfma<T>::mma(ao[u] * m, bo[u], acc);
+      }
+    };
+    const int64_t nfull = (r1 - r0) / STEP, nchunks = (r1 - r0 + STEP - 1) / STEP;
+    fetch(r0, a0, b0);
+    fetch(r0 + STEP, a1, b1);
+    int64_t ch = 0;
+    for (; ch + 3 <= nfull; ch += 3) {
+      fetch(r0 + (ch + 2) * STEP, a2, b2);
+      mma(a0, b0);
+      fetch(r0 + (ch + 3) * STEP, a0, b0);
+      mma(a1, b1);
+      fetch(r0 + (ch + 4) * STEP, a1, b1);
+      mma(a2, b2);
+    }
+    fetch(r0 + (ch + 2) * STEP, a2, b2);
+    if (ch < nchunks) mma_tail(r0 + ch * STEP, a0, b0);
+    if (ch + 1 < nchunks) mma_tail(r0 + (ch + 1) * STEP, a1, b1);
+    if (ch + 2 < nchunks) mma_tail(r0 + (ch + 2) * STEP, a2, b2);
+  }
+  const int groups = p.n_rel * p.heads;
+  float* slab = p.slab + ((static_cast<size_t>(item) * p.S + slice) * groups + rh) * T * T;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) slab[((q & 3) + 4 * KL * (q >> 2) + 4 * kk) * T + c] = acc[q];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// D = 4, 8: VALU.  The blocks of `valu_pass(...)` relations at a time in LDS (at most 32 KB; heads * D * D <= 4096 floats).
+__host__ __device__ inline int valu_pass(int n_rel, int heads, int D) {
+  int rc = 8192 / (heads * D * D);
+  if (rc > n_rel) rc = n_rel;
+  return rc < 1 ? 1 : rc;
+}
+
+template <int D, bool BWD>
+__global__ __launch_bounds__(256) void k_relt_valu(ReltArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float sWv[];       // [pass][heads][D][D]
+  const int tid = threadIdx.x;
+  const ReltItem& I = p.it[blockIdx.y];
+  const int H = p.heads * D, per_rel = H * D;
+  const int64_t gid = static_cast<int64_t>(blockIdx.x) * 256 + tid;  // one output element of an [n, H] slab: (row, head, j)
+  const int64_t row = gid / H;
+  const int col = static_cast<int>(gid - row * H), h = col / D, j = col % D;
+  const bool live = row < p.n_rows;
+  const float* xrow = I.x + (live ? row : p.n_rows - 1) * I.ld_x;
+  float xv[D];
+  auto load_x = [&](int colbase) {
+#pragma unroll
+    for (int u = 0; u < D / 4; ++u) {
+      const float4 q = reinterpret_cast<const float4*>(xrow + colbase)[u];
+      xv[4 * u] = q.x;
+      xv[4 * u + 1] = q.y;
+      xv[4 * u + 2] = q.z;
+      xv[4 * u + 3] = q.w;
+    }
+  };
+  if (!BWD) load_x(h * D);
+  const int rc = valu_pass(p.n_rel, p.heads, D);
+  float acc = 0.f;
+  for (int r0 = 0; r0 < p.n_rel; r0 += rc) {
+    const int nr = p.n_rel - r0 < rc ? p.n_rel - r0 : rc;
+    __syncthreads();                                     // the previous pass has been read
+    const float4* src = reinterpret_cast<const float4*>(I.w + static_cast<size_t>(r0) * per_rel);
+    for (int i = tid; i < nr * per_rel / 4; i += 256) reinterpret_cast<float4*>(sWv)[i] = src[i];
+    __syncthreads();
+    for (int rr = 0; rr < nr; ++rr) {
+      const int blk = ((r0 + rr) * p.heads + h) * D;
+      const float* wb = sWv + (rr * p.heads + h) * D * D + j;
+      if (BWD) load_x(blk);
+      else acc = 0.f;
+#pragma unroll
+      for (int i = 0; i < D; ++i) acc = fmaf(xv[i], wb[i * D], acc);
+      if (!BWD && live) I.y[row * I.ld_y + blk + j] = acc;
+    }
+  }
+  if (BWD && live) I.y[row * I.ld_y + col] = acc;
+}
+
+// thread (rh, i): row i of dA[r, h] = sum over the slice's rows of x[n, h*D + i] * dy[n, rh*D .. +D], rows in their order.
+template <int D>
+__global__ __launch_bounds__(256) void k_relt_dw_valu(ReltArgs p) {
+  const int groups = p.n_rel * p.heads;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= groups * D) return;
+  const int rh = t / D, i = t % D, h = rh % p.heads;
+  const int item = blockIdx.z, slice = blockIdx.y;
+  const ReltItem& I = p.it[item];
+  const int64_t r0 = static_cast<int64_t>(slice) * p.rows_per_slice;
+  int64_t r1 = r0 + p.rows_per_slice;
+  if (r1 > p.n_rows) r1 = p.n_rows;
+  const float* xs = I.x + h * D + i;
+  const float* ys = I.w + rh * D;
+  float acc[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) acc[j] = 0.f;
+  constexpr int U = 8;
+  for (int64_t n = r0; n < r1; n += U) {
+    float xv[U];
+    float2 yv[U][D / 2];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t row = n + u < r1 ? n + u : r1 - 1;
+      xv[u] = n + u < r1 ? xs[row * I.ld_x] : 0.f;
+#pragma unroll
+      for (int j = 0; j < D / 2; ++j) yv[u][j] = reinterpret_cast<const float2*>(ys + row * I.ld_y)[j];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int j = 0; j < D / 2; ++j) {
+        acc[2 * j] = fmaf(xv[u], yv[u][j].x, acc[2 * j]);
+        acc[2 * j + 1] = fmaf(xv[u], yv[u][j].y, acc[2 * j + 1]);
+      }
+  }
+  float* o = p.slab + ((static_cast<size_t>(item) * p.S + slice) * groups + rh) * D * D + i * D;
+#pragma unroll
+  for (int j = 0; j < D / 2; ++j) reinterpret_cast<float2*>(o)[j] = make_float2(acc[2 * j], acc[2 * j + 1]);
+}
+
+constexpr int kWidths[] = {4, 8, 16, 32, 64, 128, 256};   // = check_shape's head widths in hgt.hip
+
 int relt_check(const char* who, int n_items, const agnn_relt_item_t* items, int n_rel, int heads, int D, int64_t n_rows) {
   using namespace agnn;
   if (n_items <= 0 || n_items > AGNN_RELT_MAX_ITEMS || !items) return fail(AGNN_EINVAL, "%s: n_items=%d not in [1,%d]", who, n_items, AGNN_RELT_MAX_ITEMS);
-  if (D != kD) return fail(AGNN_EINVAL, "%s: D=%d (built for D = %d)", who, D, kD);
+  bool known = false;
+  for (int w : kWidths) known |= (D == w);
+  if (!known) return fail(AGNN_EINVAL, "%s: D=%d (the head width must be one of 4, 8, 16, 32, 64, 128, 256)", who, D);
   if (n_rel <= 0 || n_rel > 64 || heads <= 0 || heads > 64) return fail(AGNN_EINVAL, "%s: n_rel=%d heads=%d", who, n_rel, heads);
   if (n_rows < 0 || n_rows >= (int64_t{1} << 31)) return fail(AGNN_EINVAL, "%s: n_rows=%lld", who, (long long)n_rows);
   return AGNN_OK;
+}
+
+// forward (BWD = false) / input gradient (BWD = true): the kernel family of the head width
+template <bool BWD>
+int relt_launch(const char* who, const ReltArgs& p, int n_items, int D, hipStream_t s) {
+  using namespace agnn;
+  const int64_t n = p.n_rows;
+  const unsigned gy = static_cast<unsigned>(p.heads * n_items);
+  switch (D) {
+    case 4:
+    case 8: {
+      const int64_t blocks = (n * p.heads * D + 255) / 256;
+      if (blocks >= (int64_t{1} << 31)) return fail(AGNN_EINVAL, "%s: n_rows=%lld is too many at D=%d", who, (long long)n, D);
+      const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(n_items));
+      const size_t lds = static_cast<size_t>(valu_pass(p.n_rel, p.heads, D)) * p.heads * D * D * sizeof(float);
+      if (D == 4) hipLaunchKernelGGL((k_relt_valu<4, BWD>), grid, dim3(256), lds, s, p);
+      else hipLaunchKernelGGL((k_relt_valu<8, BWD>), grid, dim3(256), lds, s, p);
+      break;
+    }
+    case 16: hipLaunchKernelGGL((k_relt_tile<16, BWD>), dim3(static_cast<unsigned>((n + 63) / 64), gy), dim3(256), 0, s, p); break;
+    case 32: hipLaunchKernelGGL((k_relt_tile<32, BWD>), dim3(static_cast<unsigned>((n + 127) / 128), gy), dim3(256), 0, s, p); break;
+    case 64: hipLaunchKernelGGL(k_relt<BWD>, dim3(static_cast<unsigned>((n + 127) / 128), gy), dim3(256), 0, s, p); break;
+    case 128: hipLaunchKernelGGL((k_relt_wide<128, BWD>), dim3(static_cast<unsigned>((n + 127) / 128 * 2), gy), dim3(256), 0, s, p); break;
+    default: hipLaunchKernelGGL((k_relt_wide<256, BWD>), dim3(static_cast<unsigned>((n + 127) / 128 * 4), gy), dim3(256), 0, s, p); break;
+  }
+  return check_launch(who);
 }
 
 }  // namespace
@@ -277,9 +699,7 @@ extern "C" int agnn_relt_fwd_f32(int n_items, const agnn_relt_item_t* items, int
       return fail(AGNN_EALIGN, "relt_fwd: item %d: x / w must be 16-byte aligned, ld_x %% 4 == 0, ld_x >= heads*D, ld_y >= n_rel*heads*D", i);
     p.it[i] = ReltItem{t.x, t.w, t.y, t.ld_x, t.ld_y};
   }
-  const dim3 grid(static_cast<unsigned>((n_rows + 127) / 128), static_cast<unsigned>(heads * n_items));
-  hipLaunchKernelGGL(k_relt<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), p);
-  return check_launch("relt_fwd");
+  return relt_launch<false>("relt_fwd", p, n_items, D, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" int agnn_relt_bwd_f32(int n_items, const agnn_relt_item_t* items, int32_t n_rel, int32_t heads, int32_t D, int64_t n_rows,
@@ -297,28 +717,32 @@ extern "C" int agnn_relt_bwd_f32(int n_items, const agnn_relt_item_t* items, int
       return fail(AGNN_EALIGN, "relt_bwd: item %d: dy / wt must be 16-byte aligned, ld_dy %% 4 == 0, ld_dy >= n_rel*heads*D, ld_dx >= heads*D", i);
     p.it[i] = ReltItem{t.x, t.w, t.y, t.ld_x, t.ld_y};
   }
-  const dim3 grid(static_cast<unsigned>((n_rows + 127) / 128), static_cast<unsigned>(heads * n_items));
-  hipLaunchKernelGGL(k_relt<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), p);
-  return check_launch("relt_bwd");
+  return relt_launch<true>("relt_bwd", p, n_items, D, static_cast<hipStream_t>(stream_));
 }
 
 namespace {
 struct DwPlan { int S; int rows_per_slice; };
-DwPlan relt_dw_plan(int64_t n_rows) {
-  // up to 32 row slices of at least ~512 rows, an even number of rows per slice
-  int S = static_cast<int>((n_rows + 511) / 512);
-  if (S > 32) S = 32;
+DwPlan relt_dw_plan(int64_t n_rows, int D) {
+  // up to s_max row slices of at least ~rows_min rows.  D = 64: 32 slices of >= 512 rows, an even number of rows per slice
+  // (unchanged: the slice plan fixes the order of the sum, i.e. the bits of the result).  The slab of one slice grows with
+  // D^2 and the tiles per (relation, head) with (D/64)^2, so the wide blocks take fewer slices for the same number of waves;
+  // the narrow ones have tiny slabs and little work per row, so they take more and shorter slices.
+  const int rows_min = D <= 8 ? 64 : D <= 32 ? 256 : 512;
+  const int s_max = D <= 8 ? 256 : D <= 32 ? 64 : D == 64 ? 32 : D == 128 ? 8 : 2;
+  const int round = D == 64 ? 2 : 4;
+  int S = static_cast<int>((n_rows + rows_min - 1) / rows_min);
+  if (S > s_max) S = s_max;
   if (S < 1) S = 1;
   int rps = static_cast<int>((n_rows + S - 1) / S);
-  rps = (rps + 1) & ~1;
-  if (rps < 2) rps = 2;
+  rps = (rps + round - 1) / round * round;
+  if (rps < round) rps = round;
   return DwPlan{S, rps};
 }
 }  // namespace
 
 extern "C" size_t agnn_relt_dw_workspace_bytes(int n_items, int32_t n_rel, int32_t heads, int32_t D, int64_t n_rows) {
   if (n_items <= 0 || n_rel <= 0 || heads <= 0 || D <= 0 || n_rows <= 0) return 0;
-  const DwPlan pl = relt_dw_plan(n_rows);
+  const DwPlan pl = relt_dw_plan(n_rows, D);
   return static_cast<size_t>(n_items) * pl.S * n_rel * heads * D * D * sizeof(float) + 256;
 }
 
@@ -339,7 +763,7 @@ extern "C" int agnn_relt_dw_f32(int n_items, const agnn_relt_item_t* items, int3
   }
   const size_t need = agnn_relt_dw_workspace_bytes(n_items, n_rel, heads, D, n_rows);
   if (!workspace || workspace_bytes < need) return fail(AGNN_ENOMEM, "relt_dw: workspace %zu < %zu bytes", workspace_bytes, need);
-  const DwPlan pl = relt_dw_plan(n_rows);
+  const DwPlan pl = relt_dw_plan(n_rows, D);
   ReltArgs p{};
   p.n_rel = n_rel; p.heads = heads; p.n_rows = n_rows; p.S = pl.S; p.rows_per_slice = pl.rows_per_slice;
   p.slab = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t{255});
@@ -350,8 +774,23 @@ extern "C" int agnn_relt_dw_f32(int n_items, const agnn_relt_item_t* items, int3
       return fail(AGNN_EALIGN, "relt_dw: item %d: x / dy must be 8-byte aligned with even leading dimensions", i);
     p.it[i] = ReltItem{t.x, t.w, t.y, t.ld_x, t.ld_y};
   }
-  const dim3 grid(static_cast<unsigned>(n_rel * n_items), static_cast<unsigned>(pl.S), static_cast<unsigned>((heads + 3) / 4));
-  hipLaunchKernelGGL(k_relt_dw, grid, dim3(static_cast<unsigned>(64 * (heads < 4 ? heads : 4))), 0, s, p);
+  const unsigned S = static_cast<unsigned>(pl.S);
+  if (D <= 8) {                                    // one thread per row of a block gradient
+    const dim3 grid(static_cast<unsigned>((groups * D + 255) / 256), S, static_cast<unsigned>(n_items));
+    if (D == 4) hipLaunchKernelGGL(k_relt_dw_valu<4>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_relt_dw_valu<8>, grid, dim3(256), 0, s, p);
+  } else {                                         // one wave per job: a head (D <= 64) or a 64 x 64 tile of a head's block
+    const int jobs = D <= 64 ? heads : heads * (D / 64) * (D / 64);
+    const dim3 grid(static_cast<unsigned>(n_rel * n_items), S, static_cast<unsigned>((jobs + 3) / 4));
+    const dim3 block(static_cast<unsigned>(64 * (jobs < 4 ? jobs : 4)));
+    switch (D) {
+      case 16: hipLaunchKernelGGL(k_relt_dw_tile<16>, grid, block, 0, s, p); break;
+      case 32: hipLaunchKernelGGL(k_relt_dw_tile<32>, grid, block, 0, s, p); break;
+      case 64: hipLaunchKernelGGL(k_relt_dw<64>, grid, block, 0, s, p); break;
+      case 128: hipLaunchKernelGGL(k_relt_dw<128>, grid, block, 0, s, p); break;
+      default: hipLaunchKernelGGL(k_relt_dw<256>, grid, block, 0, s, p); break;
+    }
+  }
   if (int rc = check_launch("relt_dw")) return rc;
   for (int i = 0; i < n_items; ++i) {
     const float* slab = p.slab + static_cast<size_t>(i) * pl.S * groups * D * D;

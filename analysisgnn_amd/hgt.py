@@ -2,8 +2,8 @@
 layer stack, and the `HybridHGT` encoder the reference constructs at
 analysisgnn/models/analysis.py:445-453 (`heads=4`).  The per-edge work (scores, edge softmax over all
 incoming relations, weighted sum, and their gradients) runs on the C-ABI kernels
-`agnn_hgt_attn_*`, the per-(relation, head) D x D transforms on `agnn_relt_*` (at D = 64; torch batched
-matmuls at the other head widths), the per-type K/Q/V and output projections on `linear`.  Build-spec notes
+`agnn_hgt_attn_*`, the per-(relation, head) D x D transforms on `agnn_relt_*` (every head width in
+`HEAD_WIDTHS`), the per-type K/Q/V and output projections on `linear`.  Build-spec notes
 (parity unpinned vs graphmuse): encoders.py header."""
 from __future__ import annotations
 
@@ -63,8 +63,7 @@ def _index_tensor(ids: tuple, device) -> torch.Tensor:
     return _SEL_CACHE[key]
 
 
-HEAD_WIDTHS = (4, 8, 16, 32, 64, 128, 256)    # the head widths D the attention kernels take (csrc/hgt.hip check_shape)
-RELT_D = 64           # the head width the relation-transform kernels are built for (csrc/relt.hip)
+HEAD_WIDTHS = (4, 8, 16, 32, 64, 128, 256)    # the head widths D the attention (csrc/hgt.hip) and relation-transform (csrc/relt.hip) kernels take
 ATTN_ONE_LAUNCH = True  # A/B switch (bench.py --set hgt.ATTN_ONE_LAUNCH=False): the destination types' forward attention in one launch
 TYPE_STREAMS = True   # A/B switch (bench.py --set hgt.TYPE_STREAMS=False): the small node types' projections on a second stream
 _TYPE_STREAM: dict = {}
@@ -84,17 +83,9 @@ def _relt(op: str, items, R: int, heads: int, D: int, dev) -> None:
       fwd  y_rh = a_h @ b[r*heads + h]                  a = x [N, H], b = weight blocks [R*heads, D, D], y = x' [N, R*H]
       bwd  y_h = sum_r a_rh @ b[r*heads + h]            a = dx' [N, R*H], b = TRANSPOSED weight blocks, y = dx [N, H]
       dw   y[r*heads + h] = a_h^T @ b_rh                a = x [N, H], b = dx' [N, R*H], y = weight-block gradients [R*heads, D, D]
-    `agnn_relt_<op>_f32` at D = RELT_D, the width those kernels are built for; torch batched matmuls at any other head width."""
+    One `agnn_relt_<op>_f32` launch at every head width in HEAD_WIDTHS (csrc/relt.hip: VALU kernels at D = 4, 8, one MFMA tile per
+    block at D = 16, 32, the 32x32x2 fp32 MFMA pipeline at D = 64 and, tiled over D, at 128 and 256); any other D is an error."""
     N = items[0][0].shape[0]
-    if D != RELT_D:
-        for a, b, y in items:
-            if op == "fwd":
-                y.view(N, R, heads, D).copy_(torch.einsum("nhi,rhij->nrhj", a.view(N, heads, D), b.view(R, heads, D, D)))
-            elif op == "bwd":
-                y.view(N, heads, D).copy_(torch.einsum("nrhi,rhij->nhj", a.view(N, R, heads, D), b.view(R, heads, D, D)))
-            else:
-                y.view(R, heads, D, D).copy_(torch.einsum("nhi,nrhj->rhij", a.view(N, heads, D), b.view(N, R, heads, D)))
-        return
     lib = _lib.load()
     arr = (_lib.ReltItem * 2)()
     for it, (a, b, y) in zip(arr, items):

@@ -642,8 +642,11 @@ int agnn_gather_i64(const int64_t* src, int64_t ld_src, const int32_t* gid, int6
  *     backward  dx[n, h*D + i]            = sum_r sum_j dy[n, (r*heads + h)*D + j] * wt[((r*heads + h)*D + j)*D + i]
  *     dw        dw[((r*heads + h)*D + i)*D + j] = sum_n x[n, h*D + i] * dy[n, (r*heads + h)*D + j]
  * i.e. n_rel*heads independent [n, D] x [D, D] products on the fp32-input MFMA instead of one dense GEMM against a
- * block-diagonal weight (heads x the useful FLOPs).  D = 64.  Up to AGNN_RELT_MAX_ITEMS operands of the same shape
- * (K and V) per launch.  Item fields per entry point:
+ * block-diagonal weight (heads x the useful FLOPs).  D is one of 4, 8, 16, 32, 64, 128, 256 (the head widths of agnn_hgt_attn_*;
+ * anything else: AGNN_EINVAL): plain FMAs at D = 4, 8, one 16x16x4 / 32x32x2 fp32 MFMA tile per block at D = 16 / 32, the
+ * 32x32x2 fp32 MFMA over 64 x 64 pieces of the block at D = 64, 128, 256.  fwd / bwd: x and w 16-byte aligned, ld_x % 4 == 0;
+ * dw: x and dy 8-byte aligned, even leading dimensions (AGNN_EALIGN otherwise).  n_rows = 0: fwd / bwd write nothing, dw
+ * zero-fills its outputs.  Up to AGNN_RELT_MAX_ITEMS operands of the same shape (K and V) per launch.  Item fields per entry point:
  *     fwd: x = x [n, heads*D] (ld_x), w = blocks [n_rel*heads][D][D], y = y [n, n_rel*heads*D] (ld_y)
  *     bwd: x = dy (ld_x), w = the TRANSPOSED blocks, y = dx [n, heads*D] (ld_y)
  *     dw:  x = x (ld_x), w = dy (ld_y), y = dw blocks [n_rel*heads][D][D] (contiguous); row slices are summed in a
