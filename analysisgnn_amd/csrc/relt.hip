@@ -69,6 +69,111 @@ struct ReltArgs {
   int32_t S, rows_per_slice;
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Stages shared by the MFMA kernels.  What each one had to learn is written here, once; the kernels bind a stage to their
+// operands with a one-line lambda and otherwise only name it.
+
+// C/D layout of both MFMAs (T = 32: v_mfma_f32_32x32x2_f32, 16 registers; T = 16: v_mfma_f32_16x16x4_f32, 4 registers):
+// lane l, register q -> row (q&3) + 4*(64/T)*(q>>2) + 4*(l/T), column l % T.  `kk` = l / T; `base` (a first row, or 0) is added
+// in its own type, first.
+template <int T, class B>
+__device__ __forceinline__ constexpr B cd_row(B base, int q, int kk) { return base + (q & 3) + 4 * (64 / T) * (q >> 2) + 4 * kk; }
+
+// 64 x 64 weights on their way global -> registers -> LDS, 4 x 16 bytes per thread (`src`: the thread's first 16 bytes, the
+// others `stride` float4s apart; in LDS thread tid owns float4 tid + 256 j).  The registers are four NAMED float4s passed by
+// reference, not an array: an array captured by the kernels' lambdas stayed in scratch memory (`scratch_store` right behind
+// the loads, i.e. an s_waitcnt on them and on every store issued before them).
+__device__ __forceinline__ void fetch_w(const float4* src, int stride, float4& w0, float4& w1, float4& w2, float4& w3) {
+  w0 = src[0];
+  w1 = src[stride];
+  w2 = src[2 * stride];
+  w3 = src[3 * stride];
+}
+__device__ __forceinline__ void put_w(float* buf, int tid, const float4& w0, const float4& w1, const float4& w2, const float4& w3) {
+  float4* dst = reinterpret_cast<float4*>(buf) + tid;
+  dst[0] = w0;
+  dst[256] = w1;
+  dst[512] = w2;
+  dst[768] = w3;
+}
+
+// A operand of 64 MFMA k-steps: lane (row c32, half kk) holds the 32 consecutive inputs k = kk*32 .. kk*32 + 31 of its row
+// (the k order inside a product is free as long as the B operand uses the same one): eight 16-byte loads from `src`.
+// Where the operand is loop-invariant the kernel waits for it (wait_a) OUTSIDE the relation loop: left to the first MFMA
+// that uses it, the compiler puts an `s_waitcnt vmcnt(8)` at the top of EVERY iteration (it cannot see that a previous
+// iteration already waited), which also waits for the previous relation's 32 stores — one HBM write latency per relation,
+// the MFMA pipe idle meanwhile.
+__device__ __forceinline__ void load_a(float4 (&dst)[8], const float* src) {
+#pragma unroll
+  for (int u = 0; u < 8; ++u) dst[u] = reinterpret_cast<const float4*>(src)[u];
+}
+__device__ __forceinline__ void wait_a(float4 q) { asm volatile("" ::"v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w)); }
+
+// The 64 MFMAs of one 32 x 64 x 64 product.  The B operand B[k = kk*32 + s][j = c32 (+32)] comes from LDS (`sw` = the lane's
+// B[kk*32][c32], rows LD floats apart) in chunks of 8 k-steps, the next chunk's 16 reads issued BEFORE the 16 MFMAs of the
+// current one (left to the compiler, every k-step was `ds_read2 -> s_waitcnt lgkmcnt(0) -> 2 MFMAs` through one register
+// pair: the LDS latency of every read exposed).
+template <int LD>
+__device__ __forceinline__ void product(const float4 (&av)[8], const float* sw, f32x16& acc0, f32x16& acc1) {
+  float b0[2][8], b1[2][8];
+  auto rd = [&](int c, int slot) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      b0[slot][u] = sw[(8 * c + u) * LD];
+      b1[slot][u] = sw[(8 * c + u) * LD + 32];
+    }
+  };
+  rd(0, 0);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if (c + 1 < 4) rd(c + 1, (c + 1) & 1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const float4 q = av[2 * c + (u >> 2)];
+      const float as = (u & 3) == 0 ? q.x : (u & 3) == 1 ? q.y : (u & 3) == 2 ? q.z : q.w;
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(as, b0[c & 1][u], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(as, b1[c & 1][u], acc1, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// The 32 x 64 accumulator pair of a wave (rows row0 .. row0 + 31) -> global memory.  `o` = the lane's (row row0 + 4*kk,
+// column c32) of the output piece, rows `*ld` floats apart; `full` (wave-uniform): all 32 rows exist (the usual case).
+// `ld` and `n_rows` point INTO the kernel arguments and are read at every use: taken by value or by reference the compiler
+// reads them once up front, a different schedule from the one these kernels were measured with.
+__device__ __forceinline__ void store_pair(const f32x16& acc0, const f32x16& acc1, float* o, const int64_t* ld, bool full,
+                                           int64_t row0, int kk, const int64_t* n_rows) {
+  if (full) {                                            // straight-line: 32 stores, no per-row branch
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      float* oq = o + cd_row<32>(0, q, 0) * *ld;
+      oq[0] = acc0[q];
+      oq[32] = acc1[q];
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      if (cd_row<32>(row0, q, kk) < *n_rows) {
+        float* oq = o + cd_row<32>(0, q, 0) * *ld;
+        oq[0] = acc0[q];
+        oq[32] = acc1[q];
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Stages shared by the weight-gradient kernels.
+
+// the D x D block (relation, head) = rh of (item, slice) in the slab [items][S][n_rel*heads*D][D]
+template <int D>
+__device__ __forceinline__ float* dw_slab(const ReltArgs& p, int item, int slice, int rh) {
+  const int groups = p.n_rel * p.heads;
+  return p.slab + ((static_cast<size_t>(item) * p.S + slice) * groups + rh) * D * D;
+}
+
 template <bool BWD>
 __global__ __launch_bounds__(256) void k_relt(ReltArgs p) {
   constexpr int D = kD;
@@ -81,109 +186,39 @@ __global__ __launch_bounds__(256) void k_relt(ReltArgs p) {
   int64_t rowc = row0 + c32;
   if (rowc > p.n_rows - 1) rowc = p.n_rows - 1;
 
-  // next relation's weights on their way global -> registers -> LDS: four named registers, not an array (an array captured
-  // by the two lambdas stayed in scratch memory: `scratch_store` right behind the loads, i.e. an s_waitcnt on them and on
-  // every store issued before them)
-  float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = w0, w2 = w0, w3 = w0;
-  auto fetch_w = [&](int r) {
-    const float4* src = reinterpret_cast<const float4*>(I.w + static_cast<size_t>(r * p.heads + h) * D * D) + tid;
-    w0 = src[0];
-    w1 = src[256];
-    w2 = src[512];
-    w3 = src[768];
-  };
-  auto put_w = [&](int buf) {
-    float4* dst = reinterpret_cast<float4*>(sW[buf]) + tid;
-    dst[0] = w0;
-    dst[256] = w1;
-    dst[512] = w2;
-    dst[768] = w3;
-  };
-  // A operand of the MFMA: lane (row c32, half kk) holds the 32 consecutive inputs k = kk*32 .. kk*32 + 31 of its row (the k
-  // order inside a product is free as long as the B operand uses the same one): eight 16-byte loads.
+  // the shared stages (above), bound to this kernel's operands
+  float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = w0, w2 = w0, w3 = w0;    // the next relation's weights
+  auto fetch = [&](int r) { fetch_w(reinterpret_cast<const float4*>(I.w + static_cast<size_t>(r * p.heads + h) * D * D) + tid, 256, w0, w1, w2, w3); };
+  auto put = [&](int buf) { put_w(sW[buf], tid, w0, w1, w2, w3); };
   const float* xrow = I.x + rowc * I.ld_x + kk * 32;
-  auto load_a = [&](float4 (&dst)[8], int colbase) {
-    const float4* src = reinterpret_cast<const float4*>(xrow + colbase);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) dst[u] = src[u];
-  };
-  // C/D layout of the 32x32 MFMA: lane l, register q -> row (q&3) + 8*(q>>2) + 4*(l>>5), column l&31
+  auto load = [&](float4 (&dst)[8], int colbase) { load_a(dst, xrow + colbase); };
   const bool full = row0 + 32 <= p.n_rows;               // wave-uniform: all 32 rows of this wave exist (the usual case)
   float* const ybase = I.y + (row0 + 4 * kk) * I.ld_y + c32;
-  auto store = [&](const f32x16& acc0, const f32x16& acc1, int colbase) {
-    float* o = ybase + colbase;
-    if (full) {                                          // straight-line: 32 stores, no per-row branch
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        float* oq = o + ((q & 3) + 8 * (q >> 2)) * I.ld_y;
-        oq[0] = acc0[q];
-        oq[32] = acc1[q];
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        if (row0 + (q & 3) + 8 * (q >> 2) + 4 * kk < p.n_rows) {
-          float* oq = o + ((q & 3) + 8 * (q >> 2)) * I.ld_y;
-          oq[0] = acc0[q];
-          oq[32] = acc1[q];
-        }
-      }
-    }
-  };
-  // 64 MFMAs of one relation.  The B operand B[k = kk*32 + s][j = c32 (+32)] comes from LDS in chunks of 8 k-steps, the
-  // next chunk's 16 reads issued BEFORE the 16 MFMAs of the current one (left to the compiler, every k-step was
-  // `ds_read2 -> s_waitcnt lgkmcnt(0) -> 2 MFMAs` through one register pair: the LDS latency of every read exposed).
-  auto product = [&](const float4 (&av)[8], int buf, f32x16& acc0, f32x16& acc1) {
-    const float* sw = sW[buf] + kk * 32 * D + c32;
-    float b0[2][8], b1[2][8];
-    auto rd = [&](int c, int slot) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        b0[slot][u] = sw[(8 * c + u) * D];
-        b1[slot][u] = sw[(8 * c + u) * D + 32];
-      }
-    };
-    rd(0, 0);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (c + 1 < 4) rd(c + 1, (c + 1) & 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const float4 q = av[2 * c + (u >> 2)];
-        const float as = (u & 3) == 0 ? q.x : (u & 3) == 1 ? q.y : (u & 3) == 2 ? q.z : q.w;
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(as, b0[c & 1][u], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(as, b1[c & 1][u], acc1, 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
+  auto store = [&](const f32x16& acc0, const f32x16& acc1, int colbase) { store_pair(acc0, acc1, ybase + colbase, &I.ld_y, full, row0, kk, &p.n_rows); };
+  auto prod = [&](const float4 (&av)[8], int buf, f32x16& acc0, f32x16& acc1) { product<D>(av, sW[buf] + kk * 32 * D + c32, acc0, acc1); };
 
-  fetch_w(0);
-  put_w(0);
+  fetch(0);
+  put(0);
   float4 aA[8], aB[8];                                   // BWD: the A operand of relation r and of relation r + 1 (prefetched)
-  load_a(aA, h * D);                                     // BWD: relation 0's block is (0*heads + h)*D = h*D as well
-  // The A operand is waited for HERE, outside the relation loop: left to the first MFMA that uses it, the compiler puts an
-  // `s_waitcnt vmcnt(8)` at the top of EVERY iteration (it cannot see that a previous iteration already waited), which
-  // also waits for the previous relation's 32 stores — one HBM write latency per relation, the MFMA pipe idle meanwhile.
+  load(aA, h * D);                                       // BWD: relation 0's block is (0*heads + h)*D = h*D as well
 #pragma unroll
-  for (int u = 0; u < 8; ++u) asm volatile("" ::"v"(aA[u].x), "v"(aA[u].y), "v"(aA[u].z), "v"(aA[u].w));
+  for (int u = 0; u < 8; ++u) wait_a(aA[u]);             // FWD: loop-invariant (see load_a)
   f32x16 acc0 = {0}, acc1 = {0};
   __syncthreads();
   // one relation: [prefetch the next weights (global -> registers) and, for the input gradient, the next A operand]
   // -> 64 MFMAs -> [store] -> [weights registers -> the other LDS buffer] -> barrier
   auto relation = [&](int r, const float4 (&cur)[8], float4 (&nxt)[8]) {
     if (r + 1 < p.n_rel) {
-      fetch_w(r + 1);
-      if (BWD) load_a(nxt, ((r + 1) * p.heads + h) * D);
+      fetch(r + 1);
+      if (BWD) load(nxt, ((r + 1) * p.heads + h) * D);
     }
     if (!BWD) {
       acc0 = f32x16{0};
       acc1 = f32x16{0};
     }
-    product(cur, r & 1, acc0, acc1);
+    prod(cur, r & 1, acc0, acc1);
     if (!BWD) store(acc0, acc1, (r * p.heads + h) * D);
-    if (r + 1 < p.n_rel) put_w((r + 1) & 1);             // that buffer was last read in iteration r - 1 (barrier below)
+    if (r + 1 < p.n_rel) put((r + 1) & 1);               // that buffer was last read in iteration r - 1 (barrier below)
     __syncthreads();
   };
   if (BWD) {
@@ -273,11 +308,10 @@ __global__ __launch_bounds__(256) void k_relt_dw(ReltArgs p) {
     if (c + 2 < nchunks) mma_tail(r0 + (c + 2) * STEP, a2, b2);
   }
   // accXY: rows = input features 2*i + X, columns = output features 2*j + Y (the stride-2 split of the float2 loads)
-  const int groups = p.n_rel * p.heads;
-  float* slab = p.slab + ((static_cast<size_t>(item) * p.S + slice) * groups + rh) * D * D;
+  float* slab = dw_slab<D>(p, item, slice, rh);
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
-    const int i = (q & 3) + 8 * (q >> 2) + 4 * kk;
+    const int i = cd_row<32>(0, q, kk);
     float* o = slab + (ti * 64 + 2 * i) * D + tj * 64 + 2 * c32;
     *reinterpret_cast<float2*>(o) = make_float2(acc00[q], acc01[q]);
     *reinterpret_cast<float2*>(o + D) = make_float2(acc10[q], acc11[q]);
@@ -286,9 +320,8 @@ __global__ __launch_bounds__(256) void k_relt_dw(ReltArgs p) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // D = 128, 256: forward and input gradient.  Everything inside a unit (one 64 x 64 piece of the block: rows kc*64 .. of it,
-// columns ct*64 ..) is k_relt's relation: the lessons written there hold here (named staging registers, the A operand waited
-// for outside the loop where it is loop-invariant, LDS reads a chunk ahead of the MFMAs).  NC = D/64 is even, so the LDS buffer
-// of unit (r, kc) is kc & 1 and the k-chunk loop unrolls with every register array indexed by a constant.
+// columns ct*64 ..) is k_relt's relation, built from the same shared stages.  NC = D/64 is even, so the LDS buffer of unit
+// (r, kc) is kc & 1 and the k-chunk loop unrolls with every register array indexed by a constant.
 template <int D, bool BWD>
 __global__ __launch_bounds__(256) void k_relt_wide(ReltArgs p) {
   constexpr int NC = D / 64;
@@ -305,84 +338,27 @@ __global__ __launch_bounds__(256) void k_relt_wide(ReltArgs p) {
 
   float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = w0, w2 = w0, w3 = w0;
   const float* const wsrc = I.w + (tid >> 4) * D + ct * 64 + (tid & 15) * 4;      // this thread's 16 bytes of rows tid/16 + 16 j
-  auto fetch_w = [&](int r, int kc) {
-    const float* src = wsrc + (static_cast<size_t>(r * p.heads + h) * D + kc * 64) * D;
-    w0 = *reinterpret_cast<const float4*>(src);
-    w1 = *reinterpret_cast<const float4*>(src + 16 * D);
-    w2 = *reinterpret_cast<const float4*>(src + 32 * D);
-    w3 = *reinterpret_cast<const float4*>(src + 48 * D);
+  auto fetch = [&](int r, int kc) {
+    fetch_w(reinterpret_cast<const float4*>(wsrc + (static_cast<size_t>(r * p.heads + h) * D + kc * 64) * D), 4 * D, w0, w1, w2, w3);
   };
-  auto put_w = [&](int buf) {
-    float4* dst = reinterpret_cast<float4*>(sW[buf]) + tid;
-    dst[0] = w0;
-    dst[256] = w1;
-    dst[512] = w2;
-    dst[768] = w3;
-  };
+  auto put = [&](int buf) { put_w(sW[buf], tid, w0, w1, w2, w3); };
   const float* xrow = I.x + rowc * I.ld_x + kk * 32;
-  auto load_a = [&](float4 (&dst)[8], int colbase) {
-    const float4* src = reinterpret_cast<const float4*>(xrow + colbase);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) dst[u] = src[u];
-  };
+  auto load = [&](float4 (&dst)[8], int colbase) { load_a(dst, xrow + colbase); };
   const bool full = row0 + 32 <= p.n_rows;
   float* const ybase = I.y + (row0 + 4 * kk) * I.ld_y + c32;
-  auto store = [&](const f32x16& acc0, const f32x16& acc1, int colbase) {
-    float* o = ybase + colbase;
-    if (full) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        float* oq = o + ((q & 3) + 8 * (q >> 2)) * I.ld_y;
-        oq[0] = acc0[q];
-        oq[32] = acc1[q];
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        if (row0 + (q & 3) + 8 * (q >> 2) + 4 * kk < p.n_rows) {
-          float* oq = o + ((q & 3) + 8 * (q >> 2)) * I.ld_y;
-          oq[0] = acc0[q];
-          oq[32] = acc1[q];
-        }
-      }
-    }
-  };
-  auto product = [&](const float4 (&av)[8], int buf, f32x16& acc0, f32x16& acc1) {
-    const float* sw = sW[buf] + kk * 32 * 64 + c32;
-    float b0[2][8], b1[2][8];
-    auto rd = [&](int c, int slot) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        b0[slot][u] = sw[(8 * c + u) * 64];
-        b1[slot][u] = sw[(8 * c + u) * 64 + 32];
-      }
-    };
-    rd(0, 0);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (c + 1 < 4) rd(c + 1, (c + 1) & 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const float4 q = av[2 * c + (u >> 2)];
-        const float as = (u & 3) == 0 ? q.x : (u & 3) == 1 ? q.y : (u & 3) == 2 ? q.z : q.w;
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(as, b0[c & 1][u], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(as, b1[c & 1][u], acc1, 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
+  auto store = [&](const f32x16& acc0, const f32x16& acc1, int colbase) { store_pair(acc0, acc1, ybase + colbase, &I.ld_y, full, row0, kk, &p.n_rows); };
+  auto prod = [&](const float4 (&av)[8], int buf, f32x16& acc0, f32x16& acc1) { product<64>(av, sW[buf] + kk * 32 * 64 + c32, acc0, acc1); };
 
-  fetch_w(0, 0);
-  put_w(0);
+  fetch(0, 0);
+  put(0);
   float4 a[NC][8];                                       // the wave's 32 x D row slice (BWD: of the current relation's dy block)
 #pragma unroll
-  for (int kc = 0; kc < NC; ++kc) load_a(a[kc], h * D + kc * 64);
-  if (!BWD) {
+  for (int kc = 0; kc < NC; ++kc) load(a[kc], h * D + kc * 64);
+  if (!BWD) {                                            // loop-invariant only in the forward
 #pragma unroll
     for (int kc = 0; kc < NC; ++kc)
 #pragma unroll
-      for (int u = 0; u < 8; ++u) asm volatile("" ::"v"(a[kc][u].x), "v"(a[kc][u].y), "v"(a[kc][u].z), "v"(a[kc][u].w));
+      for (int u = 0; u < 8; ++u) wait_a(a[kc][u]);
   }
   f32x16 acc0 = {0}, acc1 = {0};
   __syncthreads();
@@ -391,16 +367,16 @@ __global__ __launch_bounds__(256) void k_relt_wide(ReltArgs p) {
 #pragma unroll
     for (int kc = 0; kc < NC; ++kc) {
       constexpr int kLast = NC - 1;
-      if (kc < kLast) fetch_w(r, kc + 1);
-      else if (more) fetch_w(r + 1, 0);
+      if (kc < kLast) fetch(r, kc + 1);
+      else if (more) fetch(r + 1, 0);
       if (!BWD && kc == 0) {
         acc0 = f32x16{0};
         acc1 = f32x16{0};
       }
-      product(a[kc], kc & 1, acc0, acc1);
-      if (BWD && more) load_a(a[kc], ((r + 1) * p.heads + h) * D + kc * 64);
+      prod(a[kc], kc & 1, acc0, acc1);
+      if (BWD && more) load(a[kc], ((r + 1) * p.heads + h) * D + kc * 64);
       if (!BWD && kc == kLast) store(acc0, acc1, (r * p.heads + h) * D + ct * 64);
-      if (kc < kLast || more) put_w((kc + 1) & 1);       // that buffer was last read in the previous unit (barrier below)
+      if (kc < kLast || more) put((kc + 1) & 1);         // that buffer was last read in the previous unit (barrier below)
       __syncthreads();
     }
   }
@@ -441,12 +417,11 @@ __global__ __launch_bounds__(256) void k_relt_tile(ReltArgs p) {
 #pragma unroll
     for (int u = 0; u < KS / 4; ++u) dst[u] = src[u];
   };
-  // C/D layout of both MFMAs: lane l, register q -> row (q&3) + 4*KL*(q>>2) + 4*(l/T), column l % T
   float* const ybase = I.y + (row0 + 4 * kk) * I.ld_y + c;
   auto store = [&](const acc_t& acc, int colbase) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-      const int rq = (q & 3) + 4 * KL * (q >> 2);
+      const int rq = cd_row<T>(0, q, 0);
       if (row0 + rq + 4 * kk < p.n_rows) ybase[rq * I.ld_y + colbase] = acc[q];
     }
   };
@@ -544,10 +519,9 @@ __global__ __launch_bounds__(256) void k_relt_dw_tile(ReltArgs p) {
     if (ch + 1 < nchunks) mma_tail(r0 + (ch + 1) * STEP, a1, b1);
     if (ch + 2 < nchunks) mma_tail(r0 + (ch + 2) * STEP, a2, b2);
   }
-  const int groups = p.n_rel * p.heads;
-  float* slab = p.slab + ((static_cast<size_t>(item) * p.S + slice) * groups + rh) * T * T;
+  float* slab = dw_slab<T>(p, item, slice, rh);
 #pragma unroll
-  for (int q = 0; q < NQ; ++q) slab[((q & 3) + 4 * KL * (q >> 2) + 4 * kk) * T + c] = acc[q];
+  for (int q = 0; q < NQ; ++q) slab[cd_row<T>(0, q, kk) * T + c] = acc[q];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -638,7 +612,7 @@ __global__ __launch_bounds__(256) void k_relt_dw_valu(ReltArgs p) {
         acc[2 * j + 1] = fmaf(xv[u], yv[u][j].y, acc[2 * j + 1]);
       }
   }
-  float* o = p.slab + ((static_cast<size_t>(item) * p.S + slice) * groups + rh) * D * D + i * D;
+  float* o = dw_slab<D>(p, item, slice, rh) + i * D;
 #pragma unroll
   for (int j = 0; j < D / 2; ++j) reinterpret_cast<float2*>(o)[j] = make_float2(acc[2 * j], acc[2 * j + 1]);
 }
@@ -649,10 +623,35 @@ int relt_check(const char* who, int n_items, const agnn_relt_item_t* items, int 
   using namespace agnn;
   if (n_items <= 0 || n_items > AGNN_RELT_MAX_ITEMS || !items) return fail(AGNN_EINVAL, "%s: n_items=%d not in [1,%d]", who, n_items, AGNN_RELT_MAX_ITEMS);
   bool known = false;
-  for (int w : kWidths) known |= (D == w);
-  if (!known) return fail(AGNN_EINVAL, "%s: D=%d (the head width must be one of 4, 8, 16, 32, 64, 128, 256)", who, D);
+  char widths[64];
+  int len = 0;
+  for (int w : kWidths) {
+    known |= (D == w);
+    len += snprintf(widths + len, sizeof(widths) - len, len ? ", %d" : "%d", w);
+  }
+  if (!known) return fail(AGNN_EINVAL, "%s: D=%d (the head width must be one of %s)", who, D, widths);
   if (n_rel <= 0 || n_rel > 64 || heads <= 0 || heads > 64) return fail(AGNN_EINVAL, "%s: n_rel=%d heads=%d", who, n_rel, heads);
   if (n_rows < 0 || n_rows >= (int64_t{1} << 31)) return fail(AGNN_EINVAL, "%s: n_rows=%lld", who, (long long)n_rows);
+  return AGNN_OK;
+}
+
+// The per-item checks and the ReltArgs fill of the three entry points (after relt_check).  x and w must be `align` bytes
+// aligned and ld_x a multiple of align/4 floats (16 and 4: the float4 loads of forward / input gradient; 8 and 2: the float2
+// loads of the weight gradient), and so must ld_y where w is read by rows through it (`w_by_rows`: the weight gradient's dy).
+// `rule` is the EALIGN message's account of all that.
+int relt_fill(const char* who, int n_items, const agnn_relt_item_t* items, int n_rel, int heads, int64_t n_rows, unsigned align,
+              bool w_by_rows, int64_t min_ld_x, int64_t min_ld_y, const char* rule, ReltArgs& p) {
+  using namespace agnn;
+  p.n_rel = n_rel; p.heads = heads; p.n_rows = n_rows;
+  const int64_t ld_mask = align / 4 - 1;
+  for (int i = 0; i < n_items; ++i) {
+    const agnn_relt_item_t& t = items[i];
+    if (!t.x || !t.w || !t.y) return fail(AGNN_EINVAL, "%s: item %d has a null pointer", who, i);
+    if ((reinterpret_cast<uintptr_t>(t.x) & (align - 1)) || (reinterpret_cast<uintptr_t>(t.w) & (align - 1)) || (t.ld_x & ld_mask) ||
+        (w_by_rows && (t.ld_y & ld_mask)) || t.ld_x < min_ld_x || t.ld_y < min_ld_y)
+      return fail(AGNN_EALIGN, "%s: item %d: %s", who, i, rule);
+    p.it[i] = ReltItem{t.x, t.w, t.y, t.ld_x, t.ld_y};
+  }
   return AGNN_OK;
 }
 
@@ -682,42 +681,30 @@ int relt_launch(const char* who, const ReltArgs& p, int n_items, int D, hipStrea
   return check_launch(who);
 }
 
+// agnn_relt_fwd_f32 (x [n, H], y [n, n_rel*H]) and agnn_relt_bwd_f32 (x = dy [n, n_rel*H], w = the transposed blocks, y = dx [n, H])
+template <bool BWD>
+int relt_run(int n_items, const agnn_relt_item_t* items, int n_rel, int heads, int D, int64_t n_rows, agnn_stream_t stream_) {
+  const char* who = BWD ? "relt_bwd" : "relt_fwd";
+  if (int rc = relt_check(who, n_items, items, n_rel, heads, D, n_rows)) return rc;
+  if (n_rows == 0) return AGNN_OK;
+  const int64_t H = static_cast<int64_t>(heads) * D;
+  ReltArgs p{};
+  const char* rule = BWD ? "dy / wt must be 16-byte aligned, ld_dy % 4 == 0, ld_dy >= n_rel*heads*D, ld_dx >= heads*D"
+                         : "x / w must be 16-byte aligned, ld_x % 4 == 0, ld_x >= heads*D, ld_y >= n_rel*heads*D";
+  if (int rc = relt_fill(who, n_items, items, n_rel, heads, n_rows, 16, false, BWD ? H * n_rel : H, BWD ? H : H * n_rel, rule, p)) return rc;
+  return relt_launch<BWD>(who, p, n_items, D, static_cast<hipStream_t>(stream_));
+}
+
 }  // namespace
 
 extern "C" int agnn_relt_fwd_f32(int n_items, const agnn_relt_item_t* items, int32_t n_rel, int32_t heads, int32_t D, int64_t n_rows,
                                  agnn_stream_t stream_) {
-  using namespace agnn;
-  if (int rc = relt_check("relt_fwd", n_items, items, n_rel, heads, D, n_rows)) return rc;
-  if (n_rows == 0) return AGNN_OK;
-  ReltArgs p{};
-  p.n_rel = n_rel; p.heads = heads; p.n_rows = n_rows;
-  const int64_t H = static_cast<int64_t>(heads) * D;
-  for (int i = 0; i < n_items; ++i) {
-    const agnn_relt_item_t& t = items[i];
-    if (!t.x || !t.w || !t.y) return fail(AGNN_EINVAL, "relt_fwd: item %d has a null pointer", i);
-    if (!aligned16(t.x) || !aligned16(t.w) || (t.ld_x & 3) || t.ld_x < H || t.ld_y < H * n_rel)
-      return fail(AGNN_EALIGN, "relt_fwd: item %d: x / w must be 16-byte aligned, ld_x %% 4 == 0, ld_x >= heads*D, ld_y >= n_rel*heads*D", i);
-    p.it[i] = ReltItem{t.x, t.w, t.y, t.ld_x, t.ld_y};
-  }
-  return relt_launch<false>("relt_fwd", p, n_items, D, static_cast<hipStream_t>(stream_));
+  return relt_run<false>(n_items, items, n_rel, heads, D, n_rows, stream_);
 }
 
 extern "C" int agnn_relt_bwd_f32(int n_items, const agnn_relt_item_t* items, int32_t n_rel, int32_t heads, int32_t D, int64_t n_rows,
                                  agnn_stream_t stream_) {
-  using namespace agnn;
-  if (int rc = relt_check("relt_bwd", n_items, items, n_rel, heads, D, n_rows)) return rc;
-  if (n_rows == 0) return AGNN_OK;
-  ReltArgs p{};
-  p.n_rel = n_rel; p.heads = heads; p.n_rows = n_rows;
-  const int64_t H = static_cast<int64_t>(heads) * D;
-  for (int i = 0; i < n_items; ++i) {
-    const agnn_relt_item_t& t = items[i];          // x = dy [n, n_rel*H], w = transposed blocks, y = dx [n, H]
-    if (!t.x || !t.w || !t.y) return fail(AGNN_EINVAL, "relt_bwd: item %d has a null pointer", i);
-    if (!aligned16(t.x) || !aligned16(t.w) || (t.ld_x & 3) || t.ld_x < H * n_rel || t.ld_y < H)
-      return fail(AGNN_EALIGN, "relt_bwd: item %d: dy / wt must be 16-byte aligned, ld_dy %% 4 == 0, ld_dy >= n_rel*heads*D, ld_dx >= heads*D", i);
-    p.it[i] = ReltItem{t.x, t.w, t.y, t.ld_x, t.ld_y};
-  }
-  return relt_launch<true>("relt_bwd", p, n_items, D, static_cast<hipStream_t>(stream_));
+  return relt_run<true>(n_items, items, n_rel, heads, D, n_rows, stream_);
 }
 
 namespace {
@@ -764,16 +751,11 @@ extern "C" int agnn_relt_dw_f32(int n_items, const agnn_relt_item_t* items, int3
   const size_t need = agnn_relt_dw_workspace_bytes(n_items, n_rel, heads, D, n_rows);
   if (!workspace || workspace_bytes < need) return fail(AGNN_ENOMEM, "relt_dw: workspace %zu < %zu bytes", workspace_bytes, need);
   const DwPlan pl = relt_dw_plan(n_rows, D);
-  ReltArgs p{};
-  p.n_rel = n_rel; p.heads = heads; p.n_rows = n_rows; p.S = pl.S; p.rows_per_slice = pl.rows_per_slice;
+  ReltArgs p{};                                    // x = x [n, H] (ld_x), w = dy [n, n_rel*H] (ld_y), y = dA blocks [groups][D][D]
+  p.S = pl.S; p.rows_per_slice = pl.rows_per_slice;
   p.slab = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t{255});
-  for (int i = 0; i < n_items; ++i) {
-    const agnn_relt_item_t& t = items[i];          // x = x [n, H] (ld_x), w = dy [n, n_rel*H] (ld_y), y = dA blocks [groups][D][D]
-    if (!t.x || !t.w || !t.y) return fail(AGNN_EINVAL, "relt_dw: item %d has a null pointer", i);
-    if ((reinterpret_cast<uintptr_t>(t.x) & 7u) || (reinterpret_cast<uintptr_t>(t.w) & 7u) || (t.ld_x & 1) || (t.ld_y & 1) || t.ld_x < H || t.ld_y < H * n_rel)
-      return fail(AGNN_EALIGN, "relt_dw: item %d: x / dy must be 8-byte aligned with even leading dimensions", i);
-    p.it[i] = ReltItem{t.x, t.w, t.y, t.ld_x, t.ld_y};
-  }
+  if (int rc = relt_fill("relt_dw", n_items, items, n_rel, heads, n_rows, 8, true, H, H * n_rel, "x / dy must be 8-byte aligned with even leading dimensions", p))
+    return rc;
   const unsigned S = static_cast<unsigned>(pl.S);
   if (D <= 8) {                                    // one thread per row of a block gradient
     const dim3 grid(static_cast<unsigned>((groups * D + 255) / 256), S, static_cast<unsigned>(n_items));
