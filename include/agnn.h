@@ -25,6 +25,8 @@
  *   agnn_gproj_*          the task heads' last Linear layers as one grouped projection (ref: models/analysis.py:486-496)
  *   agnn_adamw_f32        gradient clipping + `torch.optim.AdamW` step on the flat buffers (ref: models/analysis.py:1380-1381)
  *   agnn_multitask_ce_f32 the 21 per-task CrossEntropyLoss terms (ref: models/analysis.py:881-888)
+ *   agnn_multitask_kd_f32 the per-task distillation terms against the frozen memory model (ref: models/analysis.py:1041-1062)
+ *   agnn_ewc_f32          the EWC penalty and the Fisher accumulation over the flat buffers (ref: models/analysis.py:1440-1495)
  *   agnn_sample_hops      graphmuse `MuseNeighborLoader` batch assembly (ref: data/datamodules/analysis.py:270-293)
  *   agnn_relt_*           PyG `HGTConv` per-head relation transforms (k_rel / v_rel)
  *   agnn_hgt_attn_*       PyG `HGTConv` message/softmax/aggregate, reached through graphmuse
@@ -680,6 +682,47 @@ size_t agnn_adamw_workspace_bytes(void);
 int agnn_adamw_f32(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, float max_norm, float* step, float* norm_out, int32_t write_clipped_grad,
                    void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Knowledge distillation of the previous tasks against a frozen copy of the model, the first continual-learning term of
+ * the reference's step (ref: models/analysis.py:1052-1062: per task `F.kl_div(F.log_softmax(student / temp, 1),
+ * F.softmax(teacher / temp, 1), reduction='batchmean') * temp**2`, temp = 2, `.mean()` over the tasks, times lambda_dctn).
+ * student [n_rows, ld_s] and teacher [n_rows, ld_t] hold the tasks' logits in the same column layout (independent row
+ * strides; no alignment asked).  Task t owns the columns [seg_off[t], seg_end ? seg_end[t] : seg_off[t+1]): seg_off int32
+ * [n_tasks + 1] (device) as for agnn_multitask_ce_f32; seg_end int32 [n_tasks] (device, may be NULL) lets ascending segments
+ * leave columns between them uncovered.  With tau = temperature, q = softmax(student_t / tau), p = softmax(teacher_t / tau):
+ *     kd[t]          = tau^2 / n_rows * sum_n sum_c p (log p - log q)        both logs as x / tau - logsumexp: a teacher
+ *                                                                            probability that underflows to 0 contributes 0
+ *     total          = weight / n_tasks * sum_t kd[t]                        (device scalar; weight = the caller's lambda_dctn)
+ *     dstudent[n, c] = weight * tau / (n_rows * n_tasks) * (q - p)           d total / d student, FINISHED (incoming gradient 1)
+ * Columns c < n_cols that no segment covers are WRITTEN as 0 in dstudent [n_rows, ld_d]; the teacher gets no gradient.
+ * Three launches: the row pass (both matrices read once, the gradient written once; rows up to 1024 columns through an LDS
+ * image, wider ones from global memory with the same results), a fixed-order sum of the per-row terms per task, and the
+ * sum over the tasks in index order: bitwise reproducible.  `workspace` (agnn_kd_workspace_bytes(n_rows, n_tasks) bytes,
+ * 4-byte aligned) holds the per-row terms; it carries nothing from call to call.  n_rows == 0: kd and total are set to 0.
+ * The offsets are device data and are not checked here: the caller guarantees 0 <= start < end <= n_cols, ascending.
+ * ------------------------------------------------------------------------------------------ */
+size_t agnn_kd_workspace_bytes(int64_t n_rows, int32_t n_tasks);
+int agnn_multitask_kd_f32(const float* student, int64_t ld_s, const float* teacher, int64_t ld_t, const int32_t* seg_off,
+                          const int32_t* seg_end, int32_t n_tasks, int64_t n_rows, int32_t n_cols, float temperature,
+                          float weight, float* dstudent, int64_t ld_d, float* kd, float* total, void* workspace,
+                          size_t workspace_bytes, agnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Elastic weight consolidation over flat fp32 buffers of one layout (parameters, their snapshot, the Fisher estimate, the
+ * gradient), the second continual-learning term (ref: models/analysis.py:1479-1495 `ewc_penalty += (self.fisher[n] *
+ * (p - self._means[n]).pow(2)).sum()`, weighted by lambda_ewc at :1068):
+ *     penalty = sum_i fisher_i (p_i - mean_i)^2                  UNWEIGHTED, device scalar
+ *     g_i    += 2 lambda fisher_i (p_i - mean_i)                 if g != NULL: added to the gradient already there
+ * One pass (1024 per-block partial sums over slices that depend on n alone) and a fixed-order sum of the partials: bitwise
+ * reproducible.  `workspace`: agnn_ewc_workspace_bytes() bytes, nothing carried from call to call.  n == 0: penalty = 0.
+ * agnn_fisher_accum_f32: fisher_i += scale * g_i^2 — the reference's `self.fisher[n] += p.grad.data.clone().pow(2) /
+ * len_dataloader` (:1440-1455) with scale = 1 / len_dataloader.  Buffers 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+size_t agnn_ewc_workspace_bytes(void);
+int agnn_ewc_f32(const float* p, const float* mean, const float* fisher, int64_t n, float lambda, float* g, float* penalty,
+                 void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+int agnn_fisher_accum_f32(const float* g, int64_t n, float scale, float* fisher, agnn_stream_t stream);
 
 #ifdef __cplusplus
 }
