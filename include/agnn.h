@@ -27,6 +27,8 @@
  *   agnn_multitask_ce_f32 the 21 per-task CrossEntropyLoss terms (ref: models/analysis.py:881-888)
  *   agnn_multitask_kd_f32 the per-task distillation terms against the frozen memory model (ref: models/analysis.py:1041-1062)
  *   agnn_ewc_f32          the EWC penalty and the Fisher accumulation over the flat buffers (ref: models/analysis.py:1440-1495)
+ *   agnn_multitask_eval_f32 the per-task torchmetrics Accuracy / macro F1Score and the gated / joint Roman-numeral accuracies of
+ *                         the validation and test steps, as integer counters (ref: models/analysis.py:1143-1164, :1221-1282)
  *   agnn_sample_hops      graphmuse `MuseNeighborLoader` batch assembly (ref: data/datamodules/analysis.py:270-293)
  *   agnn_relt_*           PyG `HGTConv` per-head relation transforms (k_rel / v_rel)
  *   agnn_hgt_attn_*       PyG `HGTConv` message/softmax/aggregate, reached through graphmuse
@@ -723,6 +725,46 @@ size_t agnn_ewc_workspace_bytes(void);
 int agnn_ewc_f32(const float* p, const float* mean, const float* fisher, int64_t n, float lambda, float* g, float* penalty,
                  void* workspace, size_t workspace_bytes, agnn_stream_t stream);
 int agnn_fisher_accum_f32(const float* g, int64_t n, float scale, float* fisher, agnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Validation / test metrics of the task heads (ref: models/analysis.py:1143-1164, :1221-1282: per task torchmetrics
+ * `Accuracy(task="multiclass")` and `F1Score(average="macro")`, the same accuracies on the notes predicted as chord tones, and
+ * the joint Roman-numeral accuracies): the per-task argmax and the integer counters all of them are ratios of, in ONE launch.
+ * logits [n_rows, n_cols] fp32 with leading dimension ld (column-slice views are fine: 4-byte alignment is all that is asked);
+ * task t owns the columns [seg_off[t], seg_end ? seg_end[t] : seg_off[t+1]), C = end - start classes: seg_off int32
+ * [n_tasks + 1] and seg_end int32 [n_tasks] (may be NULL) on the device, as for agnn_multitask_kd_f32, not checked here (the
+ * kernel clamps them to [0, n_cols], so nothing is read or counted out of range whatever they hold).  1 <= n_tasks <=
+ * AGNN_MAX_SEG.  labels int64 [n_tasks, n_rows], task-major, or NULL (then counts must be NULL: predictions only);
+ * row_mask uint8 [n_rows] or NULL = every row.
+ *   pred [n_tasks, n_rows] int32, task-major, optional: the argmax of segment t of row r, for EVERY row whatever mask and
+ *     labels say.  torch.argmax's rule: the lowest index among equal maxima; a NaN is the maximum, the first NaN wins; -inf
+ *     is an ordinary value; -0 equals +0.
+ *   counts, int64 [agnn_eval_counts_len(n_tasks, n_cols) = 4 n_tasks + 4 + 3 n_cols], 8-byte aligned, optional:
+ *       valid[T] | correct[T] | valid_g[T] | correct_g[T] | joint_valid, joint_correct, joint_valid_g, joint_correct_g |
+ *       tp[n_cols] | n_pred[n_cols] | n_label[n_cols]            (class bins indexed by logits COLUMN)
+ *     For a row with row_mask NULL or row_mask[r] != 0, task t with label y != ignore_index and prediction p, a = start of t:
+ *       valid[t] += 1, n_pred[a + p] += 1;   0 <= y < C: n_label[a + y] += 1;   additionally p == y: correct[t] += 1, tp[a + y] += 1.
+ *     A label outside [0, C) that is not the ignore value counts as valid and wrong and touches no class bin.
+ *     gate_task >= 0: valid_g / correct_g count the same events on the rows with pred[gate_task, r] != 0 (the reference's
+ *       `mask = logits["tpc_in_label"].argmax(-1).bool()`); gate_task = -1 leaves them alone.
+ *     group_mask (bit t = task t) != 0: joint_valid counts the rows that take part and carry a non-ignored label in every
+ *       task of the group, joint_correct those of them with every task of the group correct; joint_*_g the same on gated rows.
+ *     Counters are ADDED TO, never overwritten: the caller zeroes the buffer and an epoch accumulates on the device.  Bins
+ *     of columns outside every segment stay as they are.
+ * One launch: 16 lanes per row stage the row's covered columns in LDS and reduce every segment (max, then the lowest index
+ * among the equal maxima); the counters go through a per-workgroup int32 histogram in LDS, whose non-zero bins are added to
+ * `counts` with 64-bit integer atomics — integer sums do not depend on order: bitwise reproducible.  The staged rows and the
+ * histogram share 64 KiB of LDS: n_cols <= AGNN_EVAL_MAX_COLS, AGNN_EINVAL beyond.  AGNN_EINVAL also for NULL logits /
+ * seg_off, pred and counts both NULL, counts without labels, n_tasks outside [1, AGNN_MAX_SEG], n_rows < 0, n_cols < 1 or
+ * > ld, gate_task outside [-1, n_tasks), group_mask bits at or above n_tasks; AGNN_EALIGN for counts off 8 bytes.
+ * n_rows == 0: success, no pointer is looked at.
+ * ------------------------------------------------------------------------------------------ */
+#define AGNN_EVAL_MAX_COLS 800
+size_t agnn_eval_counts_len(int32_t n_tasks, int32_t n_cols);
+int agnn_multitask_eval_f32(const float* logits, int64_t ld, const int32_t* seg_off, const int32_t* seg_end, int32_t n_tasks,
+                            int32_t n_cols, const int64_t* labels, int64_t n_rows, int64_t ignore_index,
+                            const uint8_t* row_mask, int32_t gate_task, uint32_t group_mask, int32_t* pred, int64_t* counts,
+                            agnn_stream_t stream);
 
 #ifdef __cplusplus
 }
