@@ -8,6 +8,8 @@ from typing import Optional, Sequence
 
 import torch
 
+from . import resident
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagnn_hip.so")
 MAX_SEG = 32
@@ -265,19 +267,10 @@ def require_gpu(*tensors: Optional[torch.Tensor]) -> torch.device:
     return dev
 
 
-_STATUS: dict = {}
-
-
 def status_word(device: torch.device) -> torch.Tensor:
     """The device-side status word handed to kernels that can detect an inconsistent index (agnn_csr_build): int32[1],
-    zero-initialised once per device, only ever incremented."""
-    key = str(device)
-    if key not in _STATUS:
-        if torch.cuda.is_current_stream_capturing():
-            raise AgnnError("the device status word must exist before a hipGraph capture starts (it would be re-zeroed by every "
-                            "replay): run the step once eagerly first, or call _lib.status_word(device)")
-        _STATUS[key] = torch.zeros(1, dtype=torch.int32, device=device)
-    return _STATUS[key]
+    zero-initialised once per device, only ever incremented (a resident value: it must exist before a capture starts)."""
+    return resident.value(device, ("status word",), lambda: torch.zeros(1, dtype=torch.int32, device=device))
 
 
 def check_device_status(device: torch.device) -> None:

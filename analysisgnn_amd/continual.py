@@ -20,11 +20,8 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, resident
 from .heads import unit_gradient
-
-_SEG_CACHE: Dict[tuple, tuple] = {}
-_KD_WS: Dict[str, torch.Tensor] = {}
 
 
 def _segments(offs, n_cols: int) -> Tuple[Tuple[int, ...], Optional[Tuple[int, ...]]]:
@@ -51,22 +48,9 @@ def _segments(offs, n_cols: int) -> Tuple[Tuple[int, ...], Optional[Tuple[int, .
 
 
 def _segment_tensors(starts, ends, device):
-    key = (starts, ends, str(device))
-    t = _SEG_CACHE.get(key)
-    if t is None:                            # host -> device once per layout (keeps the step graph-capturable)
-        t = _SEG_CACHE[key] = (torch.tensor(starts, dtype=torch.int32, device=device),
-                               torch.tensor(ends, dtype=torch.int32, device=device) if ends is not None else None)
-    return t
-
-
-def _kd_workspace(dev, nbytes: int) -> torch.Tensor:
-    ws = _KD_WS.get(str(dev))                # one per device: calls on one device are assumed not to overlap
-    if ws is None or ws.numel() < nbytes:
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.AgnnError("distillation_loss: the workspace must exist before a hipGraph capture starts (a buffer born under "
-                                 "capture belongs to the graph's pool): run the step once eagerly first")
-        ws = _KD_WS[str(dev)] = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
-    return ws
+    """(starts, ends or None) as int32 device tensors: host -> device once per layout, before any capture (a resident value)."""
+    return resident.value(device, ("segment table", starts, ends), lambda: (
+        torch.tensor(starts, dtype=torch.int32, device=device), torch.tensor(ends, dtype=torch.int32, device=device) if ends is not None else None))
 
 
 class _Distill(torch.autograd.Function):
@@ -91,7 +75,7 @@ class _Distill(torch.autograd.Function):
             return out[T], out
         out = torch.empty((T + 1,), dtype=torch.float32, device=dev)          # kd[T] | total
         nws = int(lib.agnn_kd_workspace_bytes(N, T))
-        ws = _kd_workspace(dev, nws)
+        ws = resident.scratch(dev, "distillation", nws, zeroed=False)
         # a one-row view may carry any stride(0): the kernel only needs it to reach the columns
         ld_s = student.stride(0) if N > 1 else max(student.stride(0), n_cols)
         ld_t = teacher.stride(0) if N > 1 else max(teacher.stride(0), n_cols)

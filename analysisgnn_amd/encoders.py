@@ -31,7 +31,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import _lib, ops, resident
 from .gru import gru_forward
 from .fused import FusedSequential, norm_act
 from .params import sage_operands, sage_operands_cat
@@ -256,14 +256,8 @@ def _head(t: torch.Tensor, n: int) -> torch.Tensor:
     return t if n >= t.shape[0] else t[:n]
 
 
-_SIDE_STREAMS: Dict[int, "torch.cuda.Stream"] = {}
-
-
 def _side_stream(dev: torch.device) -> "torch.cuda.Stream":
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    if idx not in _SIDE_STREAMS:
-        _SIDE_STREAMS[idx] = torch.cuda.Stream(device=dev, priority=SIDE_STREAM_PRIORITY)
-    return _SIDE_STREAMS[idx]
+    return resident.stream(dev, "sequence", SIDE_STREAM_PRIORITY)      # the priority as the switch reads when the stream is created
 
 
 SIDE_STREAM_PRIORITY = 0        # A/B switch (bench.py --side-priority): -1 = the sequence branch's stream ahead of the main one

@@ -5,27 +5,24 @@ function of (seed, training step, call site, element), so backward regenerates t
 from __future__ import annotations
 
 import itertools
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, resident
 from .linear import ColsumItem, all_steal, defer, deferring, leaf_refs
 
 PRE_RELU, POST_RELU = 1, 2
 ENABLED = True
-_RNG: Dict[str, torch.Tensor] = {}
 _CALL_IDS = itertools.count(1)
 
 
 def rng_state(device) -> torch.Tensor:
     """Device int64[2] = (seed, step).  `advance_rng` bumps the step (one tiny in-stream launch, graph-safe)."""
-    key = str(device)
-    if key not in _RNG:
-        _RNG[key] = torch.tensor([int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF, 0], dtype=torch.int64, device=device)
-    return _RNG[key]
+    return resident.value(device, ("dropout counter",), lambda: torch.tensor([int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF, 0],
+                                                                             dtype=torch.int64, device=device))
 
 
 def advance_rng(device) -> None:
@@ -97,9 +94,6 @@ class _NormAct(torch.autograd.Function):
         return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
 
 
-_MIX_WS: Dict[str, torch.Tensor] = {}
-
-
 def _ok16(t: torch.Tensor) -> bool:
     return t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
 
@@ -146,15 +140,11 @@ class _SkipAct(torch.autograd.Function):
         want_ds = has_x and ctx.needs_input_grad[2]
         dx = torch.empty((n, H), dtype=torch.float32, device=dev) if want_dx else None
         ds = torch.empty(1, dtype=torch.float32, device=dev) if want_ds else None
-        ws = None
-        if want_ds:
-            ws = _MIX_WS.get(str(dev))                    # one per device, zero-filled once; every call leaves its ticket at zero
-            if ws is None:
-                ws = _MIX_WS[str(dev)] = torch.zeros(int(lib.agnn_skip_act_workspace_bytes()) + 256, dtype=torch.uint8, device=dev)
-        wsp = ((ws.data_ptr() + 255) & ~255) if ws is not None else None
+        # ticket + partial sums, one per stream the node types run on (hgt.TYPE_STREAMS); every call leaves its ticket at zero
+        ws = resident.scratch(dev, "skip_act", int(lib.agnn_skip_act_workspace_bytes()), zeroed=True) if want_ds else None
         _lib.check(lib.agnn_skip_act_bwd_f32(_lib.ptr(x), x.stride(0) if has_x else 0, o.data_ptr(), o.stride(0), _lib.ptr(sk), n, H, p,
                                              1 if relu else 0, _lib.ptr(used), call_id, dz.data_ptr(), dz.stride(0), _lib.ptr(dx),
-                                             dx.stride(0) if dx is not None else 0, do.data_ptr(), do.stride(0), _lib.ptr(ds), wsp,
+                                             dx.stride(0) if dx is not None else 0, do.data_ptr(), do.stride(0), _lib.ptr(ds), _lib.ptr(ws),
                                              int(lib.agnn_skip_act_workspace_bytes()) if ws is not None else 0, _lib.stream_ptr(dev)),
                    "agnn_skip_act_bwd_f32")
         return do, dx, (ds.reshape(skip_shape) if ds is not None else None), None, None, None

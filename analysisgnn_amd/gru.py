@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, resident
 from .linear import (WgItem, all_steal, defer, defer_home, deferring, leaf_refs, mark_wgrad_async, weight_grad, weight_grad_batch,
                      wgrad_stream)
 
@@ -158,17 +158,8 @@ def gru_forward(rnn: nn.GRU, x: torch.Tensor, training: bool) -> torch.Tensor:
     return y
 
 
-_ONES: dict = {}
-
-
 def _ones(shape, device) -> torch.Tensor:
-    key = (tuple(shape), str(device))
-    t = _ONES.get(key)
-    if t is None:
-        if len(_ONES) >= 8:
-            _ONES.pop(next(iter(_ONES)))
-        t = _ONES[key] = torch.ones(shape, dtype=torch.float32, device=device)
-    return t
+    return resident.value(device, ("ones", tuple(shape)), lambda: torch.ones(shape, dtype=torch.float32, device=device), fill=True)
 
 
 class _StackPairs(torch.autograd.Function):

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, resident
 from .fused import grouped_norm_act
 from .linear import all_steal, defer, deferring, leaf_refs, linear, mark_wgrad_async, wgrad_stream
 from .params import cat_rows, stack_rows
@@ -110,11 +110,8 @@ GPROJ_ENABLED = True     # A/B switch for benchmarking
 
 
 def _offs_tensor(offs: Sequence[int], device) -> torch.Tensor:
-    key = (tuple(offs), str(device))
-    t = _OFFS_CACHE.get(key)
-    if t is None:                            # host -> device once per head layout (keeps the step graph-capturable)
-        t = _OFFS_CACHE[key] = torch.tensor(list(offs), dtype=torch.int32, device=device)
-    return t
+    """int32 offsets on the device: host -> device once per head layout, before any capture (a resident value)."""
+    return resident.value(device, ("offset table", tuple(offs)), lambda: torch.tensor(list(offs), dtype=torch.int32, device=device))
 
 
 class _GroupedProj(torch.autograd.Function):
@@ -344,10 +341,6 @@ def multitask_cross_entropy(logits: torch.Tensor, offs: Sequence[int], labels: t
     return _MultiTaskCE.apply(logits, labels, _offs_tensor(offs, logits.device), label_smoothing, ignore_index, full)
 
 
-_OFFS_CACHE: Dict[tuple, torch.Tensor] = {}
-_LOSS_WS: Dict[str, torch.Tensor] = {}
-
-
 def _check_labels(labels: torch.Tensor, T: int, N: int) -> torch.Tensor:
     """The kernels read labels as int64 [T, N]; anything else would be reinterpreted, not converted."""
     if labels.dtype != torch.int64:
@@ -357,7 +350,6 @@ def _check_labels(labels: torch.Tensor, T: int, N: int) -> torch.Tensor:
     return labels.contiguous()
 
 
-_UNIT_GRAD: dict = {}
 FINAL_GRADIENTS = True    # A/B switch: False = the round-2 flow (unscaled gradient forward, agnn_train_loss_bwd_f32 backward)
 
 
@@ -366,12 +358,7 @@ def unit_gradient(device) -> torch.Tensor:
     by identity, without reading the value — that the incoming gradient is one, so the gradients finished in the forward
     launches are handed on as they are (no launch).  Any other gradient tensor (the fresh ones `loss.backward()` fills, a
     loss scaled for gradient accumulation) takes the general path: three element-wise multiplies.  Never written to."""
-    dev = torch.device(device)
-    key = (dev.type, dev.index if dev.index is not None else (torch.cuda.current_device() if dev.type == "cuda" else 0))
-    t = _UNIT_GRAD.get(key)
-    if t is None:
-        t = _UNIT_GRAD[key] = torch.ones((), dtype=torch.float32, device=dev)
-    return t
+    return resident.value(device, ("unit gradient",), lambda: torch.ones((), dtype=torch.float32, device=device))
 
 
 class _TrainLoss(torch.autograd.Function):
@@ -395,10 +382,8 @@ class _TrainLoss(torch.autograd.Function):
             if tp.numel() != T:
                 raise _lib.AgnnError(f"task_param must have {T} entries, got {tp.numel()}")
         lib = _lib.load()
-        ws = _LOSS_WS.get(str(dev))                           # one per device: calls on one device are assumed not to overlap
-        if ws is None:                                        # zero-filled once; every call leaves it zero-filled
-            ws = _LOSS_WS[str(dev)] = torch.zeros(int(lib.agnn_train_loss_workspace_bytes()) + 256, dtype=torch.uint8, device=dev)
-        wsp = (ws.data_ptr() + 255) & ~255
+        # one per device and stream lane, zero-filled once; every call leaves it zero-filled.  Held until the launch.
+        ws = resident.scratch(dev, "train_loss", int(lib.agnn_train_loss_workspace_bytes()), zeroed=True)
         row_loss = torch.empty((T, N), dtype=torch.float32, device=dev)
         out = torch.empty((4 * T + 1,), dtype=torch.float32, device=dev)      # loss[T] | inv_cnt[T] | total | wscale[T] | dparam[T]
         dlogits = torch.empty_like(logits)
@@ -411,14 +396,14 @@ class _TrainLoss(torch.autograd.Function):
                                                      _lib.ptr(tp), float(ce_scale), row_loss.data_ptr(), dlogits.data_ptr(), out.data_ptr(),
                                                      out[T:].data_ptr(), out[2 * T:].data_ptr(), out[2 * T + 1:].data_ptr(),
                                                      out[3 * T + 1:].data_ptr(), _lib.ptr(dfeat), dfeat.stride(0) if dfeat is not None else 0,
-                                                     wsp, int(lib.agnn_train_loss_workspace_bytes()), _lib.stream_ptr(dev)),
+                                                     ws.data_ptr(), int(lib.agnn_train_loss_workspace_bytes()), _lib.stream_ptr(dev)),
                        "agnn_train_loss_final_f32")
         else:
             _lib.check(lib.agnn_train_loss_f32(logits.data_ptr(), logits.stride(0), offs_t.data_ptr(), T, labels.data_ptr(), N, float(eps),
                                                int(ignore_index), feat.data_ptr(), feat.stride(0), feat.shape[1], float(lam),
                                                _lib.ptr(tp), float(ce_scale), row_loss.data_ptr(), dlogits.data_ptr(), out.data_ptr(),
                                                out[T:].data_ptr(), out[2 * T:].data_ptr(), out[2 * T + 1:].data_ptr(),
-                                               out[3 * T + 1:].data_ptr(), wsp, int(lib.agnn_train_loss_workspace_bytes()),
+                                               out[3 * T + 1:].data_ptr(), ws.data_ptr(), int(lib.agnn_train_loss_workspace_bytes()),
                                                _lib.stream_ptr(dev)), "agnn_train_loss_f32")
         ctx.save_for_backward(dlogits, offs_t, out, feat, *([dfeat] if dfeat is not None else []))
         ctx.lam = float(lam)

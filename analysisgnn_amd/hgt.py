@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, resident
 from .encoders import TrimPlan, _HybridMixin
 from .graph import HeteroIndex, hetero_index
 from .fused import skip_act
@@ -53,28 +53,13 @@ class _RelWeight(nn.Module):
         self.weight = nn.Parameter(torch.empty(num_types, dim, dim).uniform_(-bound, bound))
 
 
-_SEL_CACHE: Dict[tuple, torch.Tensor] = {}
-
-
 def _index_tensor(ids: tuple, device) -> torch.Tensor:
-    key = (ids, str(device))
-    if key not in _SEL_CACHE:
-        _SEL_CACHE[key] = torch.tensor(list(ids), device=device)
-    return _SEL_CACHE[key]
+    return resident.value(device, ("index table", ids), lambda: torch.tensor(list(ids), device=device))
 
 
 HEAD_WIDTHS = (4, 8, 16, 32, 64, 128, 256)    # the head widths D the attention (csrc/hgt.hip) and relation-transform (csrc/relt.hip) kernels take
 ATTN_ONE_LAUNCH = True  # A/B switch (bench.py --set hgt.ATTN_ONE_LAUNCH=False): the destination types' forward attention in one launch
 TYPE_STREAMS = True   # A/B switch (bench.py --set hgt.TYPE_STREAMS=False): the small node types' projections on a second stream
-_TYPE_STREAM: dict = {}
-
-
-def _type_stream(dev) -> "torch.cuda.Stream":
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    s = _TYPE_STREAM.get(idx)
-    if s is None:
-        s = _TYPE_STREAM[idx] = torch.cuda.Stream(device=dev)
-    return s
 
 
 def _relt(op: str, items, R: int, heads: int, D: int, dev) -> None:
@@ -419,7 +404,7 @@ class HGTConv(nn.Module):
         big = max(types, key=lambda t: n_of[t])
         two = TYPE_STREAMS and dev.type == "cuda" and len(types) > 1
         main = torch.cuda.current_stream(dev) if two else None
-        side = _type_stream(dev) if two else None
+        side = resident.stream(dev, "types") if two else None
 
         def where(t):
             return torch.cuda.stream(side) if (two and t != big) else contextlib.nullcontext()

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, resident
 
 MIN_ROWS = 2048          # below this the library GEMM is fine
 MAX_OUT_IN = 512 * 1024  # above this output size the library GEMM (large tiles, no slabs) is faster (scripts/bench_wgrad.py)
@@ -26,7 +26,7 @@ ENABLED = True           # A/B switch for benchmarking
 # the launching stream: leaf parameters whose .grad is None when backward starts (FlatGradBuffer(views=False)) and
 # operands marked by `mark_wgrad_async` (built by kernel-free views or by ops that handle the stream themselves).
 # ------------------------------------------------------------------------------------------------------------
-_WG = {"enabled": False, "scope": "all", "streams": {}, "dirty": set()}
+_WG = {"enabled": False, "scope": "all", "dirty": set()}
 
 
 def enable_wgrad_overlap(flag: bool = True, scope="all") -> None:
@@ -112,10 +112,8 @@ class wgrad_stream:
     def __enter__(self):
         if not self.on:
             return self
-        idx = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
-        ws = _WG["streams"].get(idx)
-        if ws is None:
-            ws = _WG["streams"][idx] = torch.cuda.Stream(device=self.dev)
+        idx = resident.device_index(self.dev)
+        ws = resident.stream(idx, "wgrad")
         cur = torch.cuda.current_stream(self.dev)
         if cur.cuda_stream != ws.cuda_stream:           # already on it (nested use): a stream must not wait for itself in a capture
             ws.wait_stream(cur)
@@ -310,7 +308,7 @@ def join_wgrad() -> None:
     """Make the current stream wait for all weight-gradient work issued so far (no host sync)."""
     flush_all_deferred()
     for idx in list(_WG["dirty"]):
-        torch.cuda.current_stream(idx).wait_stream(_WG["streams"][idx])
+        torch.cuda.current_stream(idx).wait_stream(resident.stream(idx, "wgrad"))
     _WG["dirty"].clear()
     for s in list(_WG.get("join", {}).values()):
         cur = torch.cuda.current_stream(s.device)

@@ -284,3 +284,51 @@ def test_destination_types_in_one_attention_launch_give_the_same_layer():
     for k in res[0][0]:
         assert torch.equal(res[0][0][k], res[1][0][k]), k
         assert torch.equal(res[0][1][k], res[1][1][k]), k
+
+
+def test_type_streams_leave_every_gradient_unchanged():
+    """hgt.TYPE_STREAMS runs the small node types' projections and `skip_act` epilogues on a second stream, and autograd replays
+    each backward on its forward's stream: the note type's agnn_skip_act_bwd_f32 (several hundred blocks) and the beat type's then
+    run side by side, each counting its blocks on a ticket.  They must not share one (resident.scratch: one workspace per stream
+    lane): every gradient, each `skip` parameter's included, equals the one-stream step's to fp32 rounding, and each setting
+    reproduces its own gradients bit for bit."""
+    from analysisgnn_amd import graph, hgt
+    from analysisgnn_amd.heads import training_loss
+    from analysisgnn_amd.models import TorchAnalysisGNN
+    from analysisgnn_amd.synth import make_batch, torch_inputs
+    from test_gpu_step import _same_to_rounding
+    dev = torch.device(DEV)
+    tasks = {"cadence": 4, "localkey": 50, "hrythm": 2}
+    g = make_batch(5, 500, first_seed=21, add_beats=True, add_measures=True)
+    assert g.num_nodes["note"] >= 2000 and g.num_nodes["beat"] > 64
+    I = torch_inputs(g, 25, dev, seed=0)
+    labels = torch.stack([torch.randint(0, c, (I["batch_size"],), generator=torch.Generator().manual_seed(i)).to(dev)
+                          for i, c in enumerate(tasks.values())])
+    torch.manual_seed(0)
+    model = TorchAnalysisGNN(g.metadata(), 25, 64, 32, tasks, 3, dropout=0.0, use_jk=False, logit_fusion=False, encoder_type="hgt").to(dev).train()
+    saved = (graph.index_cache_enabled, hgt.TYPE_STREAMS)
+    graph.index_cache_enabled = False
+
+    def step(two_streams):
+        hgt.TYPE_STREAMS = two_streams
+        model.zero_grad(set_to_none=True)
+        x = model.encode(I["pitch_spelling"], I["key_signature"], I["x_dict"], I["edge_index_dict"], I["batch_dict"], I["batch_size"],
+                         I["neighbor_mask_node"], I["neighbor_mask_edge"])
+        logits, offs, _ = model.forward_clf_fused(x)
+        loss, _ = training_loss(logits, offs, labels, x, 0.1, 0.1, -1)
+        loss.backward()
+        torch.cuda.synchronize()
+        return {n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None}
+    try:
+        one, one_again = step(False), step(False)
+        two, two_again = step(True), step(True)
+    finally:
+        graph.index_cache_enabled, hgt.TYPE_STREAMS = saved
+    skips = [n for n in one if ".skip." in n]
+    assert len(skips) >= 3 and all(float(one[n].abs().max()) > 0 for n in skips), skips
+    assert set(one) == set(two)
+    for n in one:
+        assert torch.isfinite(one[n]).all(), n
+        assert torch.equal(one[n], one_again[n]), n
+        assert torch.equal(two[n], two_again[n]), n
+        _same_to_rounding(two[n], one[n], n)

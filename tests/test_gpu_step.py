@@ -510,3 +510,92 @@ def test_step_never_reads_memory_it_has_not_written(enc, defer):
         dp.defer_weight_grads(False)
         torch.use_deterministic_algorithms(saved[1], warn_only=saved[2])
         graph.index_cache_enabled, torch.utils.deterministic.fill_uninitialized_memory = saved[0], saved[3]
+
+
+def test_resident_registry_inside_a_capture():
+    """analysisgnn_amd/resident.py under a real capture: a table not seen before raises AgnnError without touching the device (the
+    capture goes on and the graph replays); scratch not seen before is handed out, zero-filled by a node of the graph, and is not
+    in the registry afterwards; a `skip_act` backward captured on such scratch (16 blocks counting on its ticket) replays, twice,
+    to the eager call's `skip` gradient, and the objective captured on such scratch (its only owner is the call: it must not be
+    freed, and handed out again as one of the call's outputs, before the launch) to the eager loss and gradients."""
+    from analysisgnn_amd import _lib, heads, resident
+    from analysisgnn_amd.fused import skip_act
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator().manual_seed(5)
+    o, x, gz = (torch.randn(64, 32, generator=gen).to(dev) for _ in range(3))
+    o.requires_grad_(True)
+    x.requires_grad_(True)
+    skip = torch.tensor([0.3], device=dev, requires_grad=True)
+    layout = (0, 3, 11, 12345)                                  # no model has these heads
+
+    offs = (0, 4, 54)
+    logits, feat = torch.randn(1000, 54, generator=gen).to(dev).requires_grad_(True), torch.randn(1000, 32, generator=gen).to(dev).requires_grad_(True)
+    labels = torch.stack([torch.randint(0, c, (1000,), generator=gen) for c in (4, 50)]).to(dev)
+
+    def grads():
+        return torch.autograd.grad(skip_act(o, x, skip, True, 0.0, True), (o, x, skip), gz)
+
+    def objective():
+        loss, _ = heads.training_loss(logits, offs, labels, feat, 0.1, 0.1, -1)
+        return (loss.detach(),) + torch.autograd.grad(loss, (logits, feat))
+
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):                               # the same ops eagerly first: no kernel is loaded inside the capture
+        do_e, dx_e, ds_e = grads()
+        obj_e = objective()
+        warm = gz * 2.0
+    torch.cuda.current_stream(dev).wait_stream(side)
+    torch.cuda.synchronize()
+    assert float(ds_e.abs()) > 0
+    assert float(obj_e[0]) > 0 and float(obj_e[1].abs().max()) > 0
+    mine = [(0, "main", "skip_act"), (0, "main", "train_loss")]
+    cached = [resident._SCRATCH.pop(k) for k in mine]           # the eager calls': the captured ones must ask for their own
+    try:
+        cg = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(cg):
+            twice = gz * 2.0
+            with pytest.raises(_lib.AgnnError, match="before a hipGraph capture starts"):
+                heads._offs_tensor(layout, dev)
+            ws = resident.scratch(dev, "not seen before", 4096, zeroed=True)
+            assert ws.numel() == 4096 and ws.data_ptr() % 256 == 0
+            do_g, dx_g, ds_g = grads()
+            obj_g = objective()
+        assert not any(k[1] == ("offset table", layout) for k in resident._VALUES)
+        assert (0, "main", "not seen before") not in resident._SCRATCH and not any(k in resident._SCRATCH for k in mine)
+        for _ in range(2):
+            ws.fill_(255)                                       # the zero fill is part of the graph: every replay starts from a zero ticket
+            ds_g.fill_(7.0)
+            for t in obj_g:
+                t.fill_(7.0)
+            cg.replay()
+            torch.cuda.synchronize()
+            assert torch.equal(twice, warm) and int(ws.count_nonzero()) == 0
+            assert torch.equal(ds_g, ds_e), (float(ds_g), float(ds_e))
+            assert torch.equal(do_g, do_e) and torch.equal(dx_g, dx_e)
+            for got, want, what in zip(obj_g, obj_e, ("loss", "d logits", "d feat")):
+                assert torch.equal(got, want), what
+    finally:
+        resident._SCRATCH.update(zip(mine, cached))
+
+
+def test_resident_scratch_is_one_per_lane():
+    """The small node types' `skip_act` backward runs on the "types" stream beside the note type's: the two count on different
+    tickets.  Any stream that is not one of the registry's is the main lane."""
+    from analysisgnn_amd import _lib, resident
+    dev = torch.device("cuda", 0)
+    nbytes = int(_lib.load().agnn_skip_act_workspace_bytes())
+    main = resident.scratch(dev, "skip_act", nbytes, zeroed=True)
+    types = resident.stream(dev, "types")
+    assert resident.stream("cuda", "types") is types and resident.lane(dev) == "main"
+    with torch.cuda.stream(types):
+        assert resident.lane(dev) == "types"
+        first = resident.scratch(dev, "skip_act", nbytes, zeroed=True)
+    with torch.cuda.stream(types):
+        again = resident.scratch(dev, "skip_act", nbytes, zeroed=True)
+    with torch.cuda.stream(torch.cuda.Stream(device=dev)):
+        assert resident.lane(dev) == "main"
+        assert resident.scratch(dev, "skip_act", nbytes, zeroed=True).data_ptr() == main.data_ptr()
+    torch.cuda.synchronize()
+    assert first.data_ptr() != main.data_ptr() and again.data_ptr() == first.data_ptr()
+    assert first.data_ptr() % 256 == 0 and main.data_ptr() % 256 == 0
