@@ -98,6 +98,16 @@ class PackItem(C.Structure):
                 ("rows", C.c_int32), ("cols", C.c_int32), ("n_src", C.c_int32), ("vec_ok", C.c_int32)]
 
 
+LR_CONSTANT, LR_WARMUP_COSINE, LR_WARMUP_EXP = 0, 1, 2
+
+
+class LrSchedule(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("warmup_steps", C.c_int32), ("count_offset", C.c_int32), ("swa_period", C.c_int32),
+                ("swa_start", C.c_int64), ("swa_anneal", C.c_int32), ("base_lr", C.c_double), ("warmup_start_lr", C.c_double),
+                ("eta_min", C.c_double), ("cos_a", C.c_double), ("cos_b", C.c_double), ("gamma", C.c_double),
+                ("decay_steps", C.c_double), ("swa_lr", C.c_double)]
+
+
 _lib: Optional[C.CDLL] = None
 
 # every exported symbol of include/agnn.h: (name, restype, argtypes)
@@ -208,6 +218,11 @@ SIGNATURES = {
     "agnn_adamw_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),
+    "agnn_lr_schedule_at": (C.c_double, [C.POINTER(LrSchedule), C.c_int64]),
+    "agnn_adamw_sched_workspace_bytes": (C.c_size_t, []),
+    "agnn_adamw_sched_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LrSchedule), C.c_float,
+                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "agnn_multitask_ce_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_float,
                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "agnn_multitask_ce_scale_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,

@@ -203,14 +203,112 @@ class FlatGradBuffer:
         return total
 
 
+class LRSchedule:
+    """Learning rate as a closed form of the optimizer's DEVICE step counter (`agnn_lr_schedule_t`, include/agnn.h): step k
+    (k optimizer steps already taken) uses `lr_at(k)`.  The hyper-parameters are constants of the launch, so a captured
+    `FlatAdamW.step` follows the schedule on every replay; changing them afterwards needs a new capture."""
+    FIELDS = ("kind", "warmup_steps", "count_offset", "base_lr", "warmup_start_lr", "eta_min", "cos_a", "cos_b", "gamma", "decay_steps")
+
+    def __init__(self, kind: int, base_lr: float, warmup_steps: int = 0, count_offset: int = 0, warmup_start_lr: float = 0.0,
+                 eta_min: float = 0.0, cos_a: float = 0.0, cos_b: float = 1.0, gamma: float = 1.0, decay_steps: float = 1.0):
+        self.kind, self.warmup_steps, self.count_offset = int(kind), int(warmup_steps), int(count_offset)
+        self.base_lr, self.warmup_start_lr, self.eta_min = float(base_lr), float(warmup_start_lr), float(eta_min)
+        self.cos_a, self.cos_b, self.gamma, self.decay_steps = float(cos_a), float(cos_b), float(gamma), float(decay_steps)
+        self.lr_at(0)                                    # the library's own validation (AgnnError)
+
+    @classmethod
+    def constant(cls, lr: float) -> "LRSchedule":
+        from . import _lib
+        return cls(_lib.LR_CONSTANT, lr)
+
+    @classmethod
+    def warmup_cosine(cls, base_lr: float, warmup_steps: int, total_steps: int, eta_min: float = 0.0) -> "LRSchedule":
+        """Step-based: linear warm-up from 0 over `warmup_steps` optimizer steps, then a half cosine that reaches `eta_min`
+        at step `total_steps`."""
+        from . import _lib
+        return cls(_lib.LR_WARMUP_COSINE, base_lr, warmup_steps, 0, 0.0, eta_min, cos_a=warmup_steps, cos_b=total_steps)
+
+    @classmethod
+    def reference_cosine(cls, base_lr: float, warmup_steps: int, max_epochs: int, eta_min: float = 0.0,
+                         warmup_start_lr: float = 0.0) -> "LRSchedule":
+        """The reference's `LinearWarmupCosineAnnealingLR` stepped once per optimizer step, taken LITERALLY
+        (models/analysis.py:104-188, "interval": "step"): the warm-up runs on k + 1, the cosine on
+        (k - warmup_steps / 3) / (max_epochs - warmup_steps / 3) — the class derives its `steps_per_epoch` as
+        current_step / last_epoch at its third `step()` call, which is 3.0.  It raises AttributeError when the warm-up ends
+        before that call (warmup_steps < 3), and so does this constructor (ValueError)."""
+        from . import _lib
+        if warmup_steps < 3:
+            raise ValueError(f"reference_cosine: warmup_steps={warmup_steps}: the reference's class fails for warm-ups shorter than 3 "
+                             "steps (it reads steps_per_epoch before its third step() call has set it)")
+        return cls(_lib.LR_WARMUP_COSINE, base_lr, warmup_steps, 1, warmup_start_lr, eta_min, cos_a=warmup_steps / 3.0, cos_b=max_epochs)
+
+    @classmethod
+    def reference_exponential(cls, base_lr: float, warmup_steps: int, decay_steps: int, gamma: float = 0.999, eta_min: float = 0.0,
+                              warmup_start_lr: float = 0.0) -> "LRSchedule":
+        """The reference's `LinearWarmupExponentialDecayLR` stepped once per optimizer step (models/analysis.py:191-275)."""
+        from . import _lib
+        return cls(_lib.LR_WARMUP_EXP, base_lr, warmup_steps, 1, warmup_start_lr, eta_min, gamma=gamma, decay_steps=decay_steps)
+
+    def to_dict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "LRSchedule":
+        return cls(**{k: d[k] for k in cls.FIELDS})
+
+    def struct(self, swa: Optional["SWA"] = None):
+        """The `agnn_lr_schedule_t` of this schedule, with `swa`'s fields (none: swa_start = -1)."""
+        from . import _lib
+        s = _lib.LrSchedule(**self.to_dict())
+        s.swa_start, s.swa_period, s.swa_anneal, s.swa_lr = -1, 1, 0, 0.0
+        if swa is not None:
+            s.swa_start, s.swa_period, s.swa_anneal, s.swa_lr = swa.start_step, swa.period, swa.anneal_epochs, swa.swa_lr
+        return s
+
+    def lr_at(self, k: int, swa: Optional["SWA"] = None) -> float:
+        """lr(k) in double, from `agnn_lr_schedule_at`: the function the kernel evaluates, compiled for the host (no GPU needed)."""
+        import ctypes
+        import math
+        from . import _lib
+        lib = _lib.load()
+        lr = float(lib.agnn_lr_schedule_at(ctypes.byref(self.struct(swa)), int(k)))
+        if math.isnan(lr):
+            raise _lib.AgnnError(f"agnn_lr_schedule_at failed: {(lib.agnn_last_error() or b'').decode()}")
+        return lr
+
+
+class SWA:
+    """Stochastic weight averaging on the optimizer's step counter: from optimizer step `start_step` on, every `period`
+    steps (one SWA "epoch") the parameters as they are before that step's update enter a running average
+    (`torch.optim.swa_utils.AveragedModel`'s default rule), and the rate anneals to `swa_lr` over `anneal_epochs` epochs as
+    `torch.optim.swa_utils.SWALR(anneal_strategy="cos")` stepped once per epoch does.  The reference's
+    `StochasticWeightAveraging(swa_lrs=5e-5, swa_epoch_start=50)` is start_step = 50 * steps_per_epoch, period =
+    steps_per_epoch; parity with Lightning's callback itself is not pinned, and BatchNorm statistics are not refreshed
+    (`update_bn`: out of scope — the encoders here normalise with LayerNorm)."""
+
+    def __init__(self, start_step: int, period: int, anneal_epochs: int = 10, swa_lr: float = 5e-5):
+        if start_step < 0 or period <= 0 or anneal_epochs < 0:
+            raise ValueError(f"SWA: start_step={start_step}, period={period}, anneal_epochs={anneal_epochs}")
+        self.start_step, self.period, self.anneal_epochs, self.swa_lr = int(start_step), int(period), int(anneal_epochs), float(swa_lr)
+
+    def to_dict(self) -> dict:
+        return dict(start_step=self.start_step, period=self.period, anneal_epochs=self.anneal_epochs, swa_lr=self.swa_lr)
+
+
 class FlatAdamW:
     """AdamW over ONE flat parameter buffer (decoupled weight decay, bias correction — torch.optim.AdamW's update
     rule, reference optimizer: models/analysis.py:1380-1381).  Parameters are re-pointed at views of the buffer,
     gradients come from a `FlatGradBuffer`, so a step is a handful of whole-model elementwise launches instead of
-    per-parameter lists: ~5 M parameters in ~130 tensors make the foreach path launch-bound."""
+    per-parameter lists: ~5 M parameters in ~130 tensors make the foreach path launch-bound.
+
+    `lr`: a float (a constant of the launch: `opt.lr = x` between EAGER steps changes it, a captured step keeps the value
+    it was captured with) or an `LRSchedule`, optionally with `swa=SWA(...)`: the rate is then evaluated on the device from
+    the step counter (`agnn_adamw_sched_f32`), so a captured step follows the schedule, and all device state (counter,
+    workspace, `last_lr` / `n_averaged`, `last_norm`, the SWA average) exists from construction on — a capture may be the
+    first thing that runs."""
 
     def __init__(self, params: Iterable[torch.nn.Parameter], grads: FlatGradBuffer, lr=1e-3, betas=(0.9, 0.999),
-                 eps=1e-8, weight_decay=1e-2):
+                 eps=1e-8, weight_decay=1e-2, swa: Optional[SWA] = None):
         self.params = [p for p in params if p.requires_grad]
         assert [id(p) for p in self.params] == [id(p) for p in grads.params], "same parameter order as the gradient buffer"
         self.grads = grads
@@ -222,18 +320,111 @@ class FlatAdamW:
             p.data = self.flat[o:o + p.numel()].view_as(p)
         self.m = torch.zeros_like(self.flat)
         self.v = torch.zeros_like(self.flat)
+        self.schedule = lr if isinstance(lr, LRSchedule) else None
+        self.swa = swa
+        if self.schedule is None:
+            if swa is not None:
+                raise ValueError("FlatAdamW: swa needs lr=LRSchedule (LRSchedule.constant(lr) for a fixed rate)")
+            return
+        self._sched = self.schedule.struct(swa)
+        self._t = torch.zeros((), dtype=torch.float32, device=dev)
+        self._state = torch.zeros(2, dtype=torch.float32, device=dev)                     # [lr the last step used, snapshots averaged]
+        self._state[0] = self.schedule.lr_at(0, swa)
+        self.last_norm = torch.zeros((), dtype=torch.float32, device=dev)
+        self.swa_flat = torch.zeros_like(self.flat) if swa is not None else None
+        if self.flat.is_cuda:
+            from . import _lib
+            self._ws = torch.empty(int(_lib.load().agnn_adamw_sched_workspace_bytes()), dtype=torch.uint8, device=dev)
+
+    @property
+    def last_lr(self) -> torch.Tensor:
+        """The rate the last step used (before the first step: lr(0)), a device scalar: reading it here costs no sync."""
+        return self._scheduled("last_lr")._state[0]
+
+    @property
+    def n_averaged(self) -> torch.Tensor:
+        """Snapshots in `swa_flat` so far, a device scalar (float, as the kernel counts them)."""
+        return self._scheduled("n_averaged")._state[1]
+
+    def current_lr(self) -> float:
+        """The rate the NEXT step will use, as a host float (float path: `opt.lr`; with a schedule this reads the counter)."""
+        if self.schedule is None:
+            return float(self.lr)
+        return self.schedule.lr_at(int(self._t.item()), self.swa)
+
+    def _scheduled(self, what: str) -> "FlatAdamW":
+        if self.schedule is None:
+            raise AttributeError(f"FlatAdamW.{what} needs lr=LRSchedule")
+        return self
+
+    @torch.no_grad()
+    def swap_swa_(self) -> None:
+        """Copy the SWA average into the flat parameters (what the callback does at the end of fit).  In place: the model's
+        parameters are views of `flat`.  BatchNorm statistics are not refreshed (`update_bn` is out of scope)."""
+        if self.swa is None:
+            raise AttributeError("FlatAdamW.swap_swa_ needs swa=SWA(...)")
+        if int(self._state[1].item()) == 0:                  # end of fit: the one host read is no cost there
+            raise RuntimeError("FlatAdamW.swap_swa_: no snapshot has been averaged yet")
+        self.flat.copy_(self.swa_flat)
+
+    def state_dict(self) -> dict:
+        """Everything a run needs to resume: parameters, moments, step counter, the schedule / SWA hyper-parameters, the average
+        and its count (clones; the layout is this optimizer's flat layout).  Not a `torch.optim` / Lightning optimizer
+        checkpoint: resuming from one of the reference's is not provided."""
+        t = getattr(self, "_t", None)
+        d = {"flat": self.flat.clone(), "m": self.m.clone(), "v": self.v.clone(),
+             "step": t.clone() if t is not None else torch.zeros((), dtype=torch.float32, device=self.flat.device),
+             "lr": None if self.schedule is not None else float(self.lr),
+             "schedule": self.schedule.to_dict() if self.schedule is not None else None,
+             "swa": self.swa.to_dict() if self.swa is not None else None}
+        if self.schedule is not None:
+            d["state"] = self._state.clone()
+        if self.swa is not None:
+            d["swa_flat"] = self.swa_flat.clone()
+        return d
+
+    @torch.no_grad()
+    def load_state_dict(self, d: dict) -> None:
+        """Write a `state_dict()` into the EXISTING buffers, so a captured graph stays valid and resumes at the saved step.
+        The schedule and SWA hyper-parameters are constants of the launch: they must equal this optimizer's."""
+        if d["flat"].numel() != self.flat.numel():
+            raise ValueError(f"load_state_dict: {d['flat'].numel()} parameters saved, {self.flat.numel()} here")
+        mine = (self.schedule.to_dict() if self.schedule is not None else None, self.swa.to_dict() if self.swa is not None else None)
+        if (d["schedule"], d["swa"]) != mine:
+            raise ValueError("load_state_dict: the saved schedule / SWA hyper-parameters differ from this optimizer's (they are constants "
+                             f"of the launch; construct FlatAdamW with them): saved {(d['schedule'], d['swa'])}, here {mine}")
+        if not hasattr(self, "_t"):
+            self._t = torch.zeros((), dtype=torch.float32, device=self.flat.device)
+        for dst, key in ((self.flat, "flat"), (self.m, "m"), (self.v, "v"), (self._t, "step")):
+            dst.copy_(d[key])
+        if self.schedule is None:
+            self.lr = d["lr"]
+        else:
+            self._state.copy_(d["state"])
+        if self.swa is not None:
+            self.swa_flat.copy_(d["swa_flat"])
 
     @torch.no_grad()
     def step(self, max_norm: float = 0.0) -> None:
         """One AdamW update; `max_norm > 0` first clips the global gradient norm (clip_grad_norm_ semantics).
-        Graph-capturable: the step counter and the bias corrections live on the device.  On a GPU the whole thing is
-        the two launches of `agnn_adamw_f32`; on CPU tensors (gloo tests) the same arithmetic in torch ops."""
+        Graph-capturable: the step counter and the bias corrections live on the device, and with an `LRSchedule` so do the
+        rate and the SWA bookkeeping.  On a GPU the whole thing is the two launches of `agnn_adamw_f32` /
+        `agnn_adamw_sched_f32`; on CPU tensors (gloo tests) the same arithmetic in torch ops."""
         if not hasattr(self, "_t"):
             self._t = torch.zeros((), dtype=torch.float32, device=self.flat.device)
         g = self.grads.flat
         if self.flat.is_cuda:
+            import ctypes
             from . import _lib
             lib = _lib.load()
+            if self.schedule is not None:
+                _lib.check(lib.agnn_adamw_sched_f32(self.flat.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                                    self.flat.numel(), ctypes.byref(self._sched), float(self.betas[0]),
+                                                    float(self.betas[1]), float(self.eps), float(self.wd), float(max_norm),
+                                                    self._t.data_ptr(), _lib.ptr(self.swa_flat), self._state.data_ptr(),
+                                                    self.last_norm.data_ptr(), 0, self._ws.data_ptr(), self._ws.numel(),
+                                                    _lib.stream_ptr(self.flat.device)), "agnn_adamw_sched_f32")
+                return
             if not hasattr(self, "_ws"):
                 self._ws = torch.empty(int(lib.agnn_adamw_workspace_bytes()), dtype=torch.uint8, device=self.flat.device)
                 self.last_norm = torch.zeros((), dtype=torch.float32, device=self.flat.device)
@@ -242,17 +433,31 @@ class FlatAdamW:
                                           float(max_norm), self._t.data_ptr(), self.last_norm.data_ptr(), 0, self._ws.data_ptr(),
                                           self._ws.numel(), _lib.stream_ptr(self.flat.device)), "agnn_adamw_f32")
             return
+        lr = self.lr
+        if self.schedule is not None:                        # the kernel's rule: lr(k) in double, rounded to float once
+            k = int(self._t)
+            lr = float(torch.tensor(self.schedule.lr_at(k, self.swa), dtype=torch.float64).float())
+            self._state[0] = lr
+            if self.swa is not None and k >= self.swa.start_step and (k - self.swa.start_step) % self.swa.period == 0:
+                n = float(self._state[1])
+                if n == 0:
+                    self.swa_flat.copy_(self.flat)
+                else:
+                    self.swa_flat.add_((self.flat - self.swa_flat) / (n + 1.0))
+                self._state[1] = n + 1.0
         if max_norm > 0:
-            self.grads.clip_norm_(max_norm)
+            total = self.grads.clip_norm_(max_norm)
+            if self.schedule is not None:
+                self.last_norm.copy_(total)
         b1, b2 = self.betas
         self._t += 1.0
         bc1 = 1.0 - (b1 ** self._t)
         bc2 = 1.0 - (b2 ** self._t)
-        self.flat.mul_(1.0 - self.lr * self.wd)
+        self.flat.mul_(1.0 - lr * self.wd)
         self.m.mul_(b1).add_(g, alpha=1.0 - b1)
         self.v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
         denom = (self.v.sqrt() / bc2.sqrt()).add_(self.eps)
-        self.flat.addcdiv_(self.m / bc1, denom, value=-self.lr)
+        self.flat.addcdiv_(self.m / bc1, denom, value=-lr)
 
 
 def enable_wgrad_overlap(flag: bool = True, scope="all") -> None:

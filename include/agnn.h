@@ -24,6 +24,8 @@
  *                         (ref: models/analysis.py:399-400, :574)
  *   agnn_gproj_*          the task heads' last Linear layers as one grouped projection (ref: models/analysis.py:486-496)
  *   agnn_adamw_f32        gradient clipping + `torch.optim.AdamW` step on the flat buffers (ref: models/analysis.py:1380-1381)
+ *   agnn_adamw_sched_f32  the same step under the reference's per-step LR schedulers and SWA, the rate a closed form of the
+ *                         device step counter (ref: models/analysis.py:104-275, :1380-1410; train/train_analysisgnn.py:243-245)
  *   agnn_multitask_ce_f32 the 21 per-task CrossEntropyLoss terms (ref: models/analysis.py:881-888)
  *   agnn_multitask_kd_f32 the per-task distillation terms against the frozen memory model (ref: models/analysis.py:1041-1062)
  *   agnn_ewc_f32          the EWC penalty and the Fisher accumulation over the flat buffers (ref: models/analysis.py:1440-1495)
@@ -684,6 +686,66 @@ size_t agnn_adamw_workspace_bytes(void);
 int agnn_adamw_f32(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, float max_norm, float* step, float* norm_out, int32_t write_clipped_grad,
                    void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The same step with the learning rate as a CLOSED FORM OF THE DEVICE STEP COUNTER, and stochastic weight averaging.
+ * agnn_adamw_f32 takes lr as a host float: inside a captured hipGraph it is a constant of the kernel node, while the
+ * reference changes the rate after every optimizer step (`LinearWarmupCosineAnnealingLR` with "interval": "step",
+ * models/analysis.py:104-188, :1380-1410; `LinearWarmupExponentialDecayLR`, :191-275) and `--use_swa` adds
+ * `StochasticWeightAveraging(swa_lrs=5e-5, swa_epoch_start=50)` (train/train_analysisgnn.py:243-245).  Here the schedule's
+ * hyper-parameters are a host struct passed by value into the launch, and the launch that advances the counter evaluates it.
+ *
+ * Step index: k = optimizer steps already taken = *step before this call's increment; step k uses lr(k).
+ * Below the SWA start (k < swa_start, or swa_start < 0), with c = k + count_offset, b = base_lr, s = warmup_start_lr:
+ *     c < warmup_steps (both warm-up kinds)   lr = s + (b - s) * c / warmup_steps
+ *     AGNN_LR_WARMUP_COSINE, otherwise        lr = eta_min + (b - eta_min) / 2 * (1 + cos(pi * (k - cos_a) / (cos_b - cos_a)))
+ *     AGNN_LR_WARMUP_EXP, otherwise           lr = max(eta_min, b * gamma^((c - warmup_steps) / decay_steps))
+ *     AGNN_LR_CONSTANT                        lr = b
+ * The reference's cosine class stepped once per optimizer step is count_offset = 1, cos_a = warmup_steps / 3, cos_b =
+ * max_epochs (its `steps_per_epoch` is current_step / last_epoch at its third step() call: 3.0; it raises AttributeError
+ * for warmup_steps < 3, which the host constructor dp.LRSchedule.reference_cosine refuses); its exponential class is
+ * count_offset = 1.
+ * From the SWA start on (k >= swa_start), with e = (k - swa_start) / swa_period (integer division):
+ *     alpha = (1 - cos(pi * min(1, e / swa_anneal))) / 2          (swa_anneal == 0: alpha = 1)
+ *     lr    = (1 - alpha) * lr(swa_start) of the schedule above + alpha * swa_lr
+ * the closed form of `torch.optim.swa_utils.SWALR(anneal_strategy="cos")` created at step swa_start and stepped once per
+ * swa_period optimizer steps.  When (k - swa_start) % swa_period == 0 the parameters AS THEY ARE BEFORE this step's update
+ * enter the average: the first snapshot is avg = p, later ones avg += (p - avg) / (n + 1), the default rule of
+ * `torch.optim.swa_utils.AveragedModel`; n lives on the device.  The contract is these two torch classes driven as
+ * described; parity with Lightning's StochasticWeightAveraging callback (which also swaps the averaged weights in at the
+ * end of fit and refreshes BatchNorm statistics, `update_bn`) is NOT pinned, and `update_bn` is not provided.  Resuming
+ * from an optimizer checkpoint written by the reference (Lightning / torch.optim layout) is not pinned either: the host
+ * side saves and loads these flat buffers (dp.FlatAdamW.state_dict).
+ *
+ * lr is evaluated once per step, in double (cospi on the phase), rounded to float once, handed to the update launch through
+ * the workspace and written to state[0].  `state` (device float[2]): [0] the rate the last step used, [1] the number of
+ * snapshots averaged so far (the caller zeroes it once).  swa_avg (device, n floats, 16-byte aligned) is NULL iff
+ * swa_start < 0; steps that take no snapshot do not touch it.  The schedule is a launch constant: changing its
+ * hyper-parameters needs a new capture; advancing, resuming (write *step, state, swa_avg, m, v in place) and averaging do
+ * not.  A constant schedule gives agnn_adamw_f32's results bit for bit (one update body).  Two launches; a snapshot step
+ * moves 9 streams of 4n bytes instead of 7.  The counter is a float: exact up to 2^24 steps, like agnn_adamw_f32's.
+ * agnn_lr_schedule_at evaluates the same function on the host (no GPU needed); NaN (and a message) for an invalid schedule
+ * or k < 0.
+ * ------------------------------------------------------------------------------------------ */
+#define AGNN_LR_CONSTANT      0
+#define AGNN_LR_WARMUP_COSINE 1
+#define AGNN_LR_WARMUP_EXP    2
+typedef struct {
+  int32_t kind;          /* AGNN_LR_* */
+  int32_t warmup_steps;  /* W >= 0 */
+  int32_t count_offset;  /* c0: warm-up / decay run on c = k + c0 */
+  int32_t swa_period;    /* P > 0 optimizer steps per SWA "epoch" */
+  int64_t swa_start;     /* K; < 0: no SWA */
+  int32_t swa_anneal;    /* Na >= 0 epochs of cosine annealing towards swa_lr */
+  double base_lr, warmup_start_lr, eta_min, cos_a, cos_b, gamma, decay_steps, swa_lr;
+} agnn_lr_schedule_t;
+
+double agnn_lr_schedule_at(const agnn_lr_schedule_t* sched /* (host) */, int64_t k);
+size_t agnn_adamw_sched_workspace_bytes(void);
+int agnn_adamw_sched_f32(float* p, float* g, float* m, float* v, int64_t n, const agnn_lr_schedule_t* sched /* (host) */,
+                         float beta1, float beta2, float eps, float weight_decay, float max_norm, float* step, float* swa_avg,
+                         float* state, float* norm_out, int32_t write_clipped_grad, void* workspace, size_t workspace_bytes,
+                         agnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Knowledge distillation of the previous tasks against a frozen copy of the model, the first continual-learning term of
