@@ -89,7 +89,8 @@ class ColsumItem(C.Structure):
                 ("dbeta", C.c_void_p)]
 
 
-WGRAD_BATCH_MAX = 16
+WGRAD_BATCH_MAX = 16          # products (weight gradients, column sums) per batched launch
+WGRAD_BATCH_MAX_ITEMS = 24    # agnn_wgrad_batch_f32's items: a product in two column blocks (linear.linear2) is two of them
 PACK_MAX_SRC = 8
 
 
@@ -162,6 +163,13 @@ SIGNATURES = {
                                    C.c_int64, C.c_void_p]),
     "agnn_gemm_nn_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                    C.c_int64, C.c_void_p]),
+    "agnn_gemm_nt2_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "agnn_pool_cat_norm_f32": (C.c_int, [C.POINTER(Rel), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "agnn_pool_cat_bwd_f32": (C.c_int, [C.POINTER(Rel), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                        C.c_int64, C.c_void_p]),
     "agnn_absdiff_fwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_void_p]),
     "agnn_absdiff_bwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,

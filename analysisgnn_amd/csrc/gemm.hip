@@ -34,6 +34,9 @@ struct GemmArgs {
   int64_t ld_a, ld_w, ld_c;
   int32_t M, N, K;
   int32_t tiles_n;
+  const float* a1;          // TWO: columns [K0, K) of the first operand live here (agnn_gemm_nt2_f32)
+  int64_t ld_a1;
+  int32_t K0;
 };
 
 // BN = 128: a wave owns 64 x 64 (four accumulators); BN = 64: 64 x 32 (two) — twice the workgroups, for shapes whose 128 x 128 tiling
@@ -42,7 +45,9 @@ struct GemmArgs {
 // NN = true: the second operand is K-MAJOR, w[K, N] (C = A w + b) — the input-gradient product dX = dY W with the weight as it
 // lies in memory.  Its tile sits in LDS as it is read, [k][n] (row stride BN + 8: the two lane halves, 4 k rows apart, fall into
 // different bank halves), and a lane's four k values of a fragment come from four 4-byte reads (32 consecutive n per half: no conflict)
-template <int BN, bool NN>
+// TWO = true: the first operand is [a | a1], two matrices with their own row strides that are never concatenated — the running row
+// pointers switch base at k = K0 (a multiple of BK: no step straddles the seam).  Same k order, same MFMAs: the same bits as on the cat
+template <int BN, bool NN, bool TWO = false>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
   constexpr int NJ = BN / 64;              // 32-column accumulators per wave
   constexpr int LDN = BN + 8;
@@ -62,6 +67,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
   const int sr = tid >> 2, sk = 4 * (tid & 3);
   const float* pa0 = g.a + static_cast<int64_t>(min(row0 + sr, g.M - 1)) * g.ld_a + sk;          // rows past M: clamped, never stored
   const float* pa1 = g.a + static_cast<int64_t>(min(row0 + 64 + sr, g.M - 1)) * g.ld_a + sk;
+  const float* qa0 = TWO ? g.a1 + static_cast<int64_t>(min(row0 + sr, g.M - 1)) * g.ld_a1 + sk : nullptr;
+  const float* qa1 = TWO ? g.a1 + static_cast<int64_t>(min(row0 + 64 + sr, g.M - 1)) * g.ld_a1 + sk : nullptr;
+#define A0_AT(k) (TWO ? ((k) < g.K0 ? pa0 + (k) : qa0 + ((k) - g.K0)) : pa0 + (k))
+#define A1_AT(k) (TWO ? ((k) < g.K0 ? pa1 + (k) : qa1 + ((k) - g.K0)) : pa1 + (k))
   const int so0 = sr * LDT + sk, so1 = (64 + sr) * LDT + sk;
   // second operand: NT — rows col0 + (t / 4) (+ 64) of w[N, K], as the first; NN — k rows (t / (BN / 4)) (+ 8) of w[K, N], 16 bytes of n each
   const int nr = NN ? tid / (BN / 4) : 0, nc = NN ? 4 * (tid % (BN / 4)) : 0;
@@ -101,13 +110,13 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
   xa0 = LD4(pa0); xa1 = LD4(pa1); xw0 = LD4(pw0); xw1 = LD4(pw1);
   {
     const int k1 = min(BK, last);
-    ya0 = LD4(pa0 + k1); ya1 = LD4(pa1 + k1); yw0 = LD4(pw0 + k1 * wmul); yw1 = LD4(pw1 + k1 * wmul);
+    ya0 = LD4(A0_AT(k1)); ya1 = LD4(A1_AT(k1)); yw0 = LD4(pw0 + k1 * wmul); yw1 = LD4(pw1 + k1 * wmul);
   }
   ST4(&sA[0][so0], xa0); ST4(&sA[0][so1], xa1); ST4(&sB[0][sbo0], xw0);
   if (NJ == 2) ST4(&sB[0][sbo1], xw1);
   {
     const int k2 = min(2 * BK, last);
-    xa0 = LD4(pa0 + k2); xa1 = LD4(pa1 + k2); xw0 = LD4(pw0 + k2 * wmul); xw1 = LD4(pw1 + k2 * wmul);
+    xa0 = LD4(A0_AT(k2)); xa1 = LD4(A1_AT(k2)); xw0 = LD4(pw0 + k2 * wmul); xw1 = LD4(pw1 + k2 * wmul);
   }
   __syncthreads();
   fa0 = LD4(&sA[0][fa]); fa1 = LD4(&sA[0][fa + 32 * LDT]);
@@ -134,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
     if (NJ == 2) ST4(&sB[(CUR) ^ 1][sbo1], SW1);                                                           \
     {                                                                                                      \
       const int k3 = min(((KB) + 3) * BK, last);                                                           \
-      SA0 = LD4(pa0 + k3); SA1 = LD4(pa1 + k3); SW0 = LD4(pw0 + k3 * wmul); SW1 = LD4(pw1 + k3 * wmul);    \
+      SA0 = LD4(A0_AT(k3)); SA1 = LD4(A1_AT(k3)); SW0 = LD4(pw0 + k3 * wmul); SW1 = LD4(pw1 + k3 * wmul);    \
     }                                                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                                     \
     MFMA_BLOCK(ga0, ga1, gb0, gb1)                                                                         \
@@ -149,6 +158,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
   }
   if (kb < nk) STEP(0, kb, ya0, ya1, yw0, yw1)
 #undef STEP
+#undef A0_AT
+#undef A1_AT
 #undef BFRAG
 #undef MFMA_BLOCK
 #undef LD4
@@ -174,23 +185,30 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
 }  // namespace
 
 namespace {
+// a1 != nullptr: the first operand is [a (K0 columns) | a1 (K - K0 columns)]
 int launch_gemm(bool nn, const float* a, int64_t ld_a, const float* w, int64_t ld_w, const float* bias, int64_t M, int32_t N, int32_t K,
-                float* c, int64_t ld_c, agnn_stream_t stream_, const char* who) {
+                float* c, int64_t ld_c, agnn_stream_t stream_, const char* who, const float* a1 = nullptr, int64_t ld_a1 = 0, int32_t K0 = 0) {
   using namespace agnn;
   if (M < 0 || M >= (int64_t{1} << 31) || N <= 0 || K <= 0) return fail(AGNN_EINVAL, "%s: bad sizes M=%lld N=%d K=%d", who, (long long)M, N, K);
   if ((N % 64) || (K % BK)) return fail(AGNN_EINVAL, "%s: N=%d must be a multiple of 64 and K=%d of %d", who, N, K, BK);
   if (M == 0) return AGNN_OK;
   if (!a || !w || !c) return fail(AGNN_EINVAL, "%s: null argument", who);
-  if (!aligned16(a) || !aligned16(w) || (ld_a & 3) || (ld_w & 3) || ld_a < K || ld_w < (nn ? N : K) || ld_c < N)
+  const bool two = a1 != nullptr;
+  if (two && (!aligned16(a1) || (ld_a1 & 3) || ld_a1 < K - K0))
+    return fail(AGNN_EALIGN, "%s: the second column block must be 16-byte aligned with a leading dimension that is a multiple of 4 and covers its row", who);
+  if (!aligned16(a) || !aligned16(w) || (ld_a & 3) || (ld_w & 3) || ld_a < (two ? K0 : K) || ld_w < (nn ? N : K) || ld_c < N)
     return fail(AGNN_EALIGN, "%s: operands must be 16-byte aligned with leading dimensions that are multiples of 4 and cover a row (C: >= N)", who);
   const int64_t tiles_m = (M + BM - 1) / BM;
   const int64_t groups = (tiles_m + 7) / 8;
   // 64-wide column tiles when 128-wide ones would leave the chip with fewer than two workgroups per CU (or N is not a multiple of 128)
   const bool narrow = (N % 128) != 0 || tiles_m * (N / 128) < 512;
-  GemmArgs g{a, w, bias, c, ld_a, ld_w, ld_c, static_cast<int32_t>(M), N, K, narrow ? N / 64 : N / 128};
+  GemmArgs g{a, w, bias, c, ld_a, ld_w, ld_c, static_cast<int32_t>(M), N, K, narrow ? N / 64 : N / 128, a1, ld_a1, two ? K0 : K};
   const dim3 grid(static_cast<unsigned>(groups * 8 * g.tiles_n));
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  if (nn) {
+  if (two) {
+    if (narrow) hipLaunchKernelGGL((k_gemm_nt<64, false, true>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL((k_gemm_nt<128, false, true>), grid, dim3(256), 0, s, g);
+  } else if (nn) {
     if (narrow) hipLaunchKernelGGL((k_gemm_nt<64, true>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((k_gemm_nt<128, true>), grid, dim3(256), 0, s, g);
   } else {
@@ -209,4 +227,13 @@ extern "C" int agnn_gemm_nt_f32(const float* a, int64_t ld_a, const float* w, in
 extern "C" int agnn_gemm_nn_f32(const float* a, int64_t ld_a, const float* w, int64_t ld_w, const float* bias, int64_t M, int32_t N,
                                 int32_t K, float* c, int64_t ld_c, agnn_stream_t stream_) {
   return launch_gemm(true, a, ld_a, w, ld_w, bias, M, N, K, c, ld_c, stream_, "gemm_nn");
+}
+
+extern "C" int agnn_gemm_nt2_f32(const float* a0, int64_t ld_a0, int32_t K0, const float* a1, int64_t ld_a1, int32_t K1, const float* w,
+                                 int64_t ld_w, const float* bias, int64_t M, int32_t N, float* c, int64_t ld_c, agnn_stream_t stream_) {
+  using namespace agnn;
+  if (K0 <= 0 || K1 <= 0 || (K0 % BK) || (K1 % BK) || K0 > (1 << 30) || K1 > (1 << 30))
+    return fail(AGNN_EINVAL, "gemm_nt2: K0=%d and K1=%d must be positive multiples of %d", K0, K1, BK);
+  if (M > 0 && !a1) return fail(AGNN_EINVAL, "gemm_nt2: null argument");
+  return launch_gemm(false, a0, ld_a0, w, ld_w, bias, M, N, K0 + K1, c, ld_c, stream_, "gemm_nt2", a1, ld_a1, K0);
 }

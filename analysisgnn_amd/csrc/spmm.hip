@@ -33,6 +33,18 @@ struct SpmmArgs {
   int32_t col_limit;
   uint32_t flags;
   int32_t self_rows;   // rows of `self`; rows beyond take no self term (AGNN_SPMM_ROOT: the root slot may be shorter than the output)
+  // the join block's two launches (k_spmm_fast7's EPI != 0; unused otherwise)
+  int32_t pool_rows;   // rows at or beyond it have no neighbours
+  float eps;           // EPI_JOIN: y = LayerNorm([self | out]) * gamma + beta over the 2H floats the wave holds
+  const float* gamma;
+  const float* beta;
+  float* y;
+  int64_t ld_y;
+  float* mean;
+  float* rstd;
+  const float* self2;  // EPI_SELF2: one more addend, self2_scale[row] * self2[row]
+  int64_t ld_self2;
+  const float* self2_scale;
 };
 
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -338,7 +350,14 @@ __global__ __launch_bounds__(256) void k_spmm_fast(RelTable t, SpmmArgs a) {
 // column != row: the onset pooling, models/analysis.py:581-584).  They are evaluated once per column-id vector and kept
 // as a 64-bit wave mask in SGPRs: a neighbour's "keep" bit is a scalar shift, the valid count one s_bcnt1.
 // One row per wave: consecutive rows sharing one index phase measured slower (see launch_fast).
+// EPI selects an epilogue for the join block between the encoder and project_enc (agnn_pool_cat_norm_f32 and its backward):
+//   EPI_JOIN   (shared slot, self, mean): the wave holds x_i and pooled_i, i.e. the whole row u_i = [x_i | pooled_i] of the
+//              concatenation in k_na_fwd's lane layout: it writes u_i, and LayerNorm(u_i) with its two statistics, in place of the
+//              pooled row alone.  Rows at or beyond pool_rows have no neighbours and take pooled_i = x_i.
+//   EPI_SELF2  (shared slot, root): out_i = root_i + (self2_scale[i] * self2_i + sum_r (...)), each step rounded — the pooling's
+//              neighbour, self and cat gradients in one launch, summed as the three launches it replaces summed them.  Rows at or beyond pool_rows have no neighbours.
 // ------------------------------------------------------------------------------------------
+constexpr int EPI_NONE = 0, EPI_JOIN = 1, EPI_SELF2 = 2;
 struct FastTable {
   const int32_t* rowptr[AGNN_MAX_SEG + 3];
   const int32_t* rowend[AGNN_MAX_SEG + 3];     // per-row ends: the relation's rowend array, or rowptr + 1
@@ -358,8 +377,17 @@ __device__ __forceinline__ float4 f4_keep(bool keep, const float4& v) {
   return make_float4(keep ? v.x : 0.f, keep ? v.y : 0.f, keep ? v.z : 0.f, keep ? v.w : 0.f);
 }
 
-template <int CH, bool HAS_CS, bool SHARED, bool SELF, bool FILT>
+// root + (w * s + acc) with every step rounded (no fused multiply-add): k_spmm_self_grad's product and sum, then autograd's add
+__device__ __forceinline__ float root_plus_self2(float root, float w, float s, float acc) {
+#pragma clang fp contract(off)
+  const float t = w * s;
+  const float u = t + acc;
+  return root + u;
+}
+
+template <int CH, bool HAS_CS, bool SHARED, bool SELF, bool FILT, int EPI = EPI_NONE>
 __global__ __launch_bounds__(256) void k_spmm_fast7(FastTable t, SpmmArgs a) {
+  static_assert(EPI == EPI_NONE || (SHARED && SELF && FILT), "the join block's epilogues sit on the shared-slot kernel with a self operand");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int vb = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);   // XCD-contiguous row slabs
@@ -379,6 +407,17 @@ __global__ __launch_bounds__(256) void k_spmm_fast7(FastTable t, SpmmArgs a) {
     const char* sp = reinterpret_cast<const char*>(a.self + static_cast<int64_t>(has ? row : 0) * a.ld_self);
 #pragma unroll
     for (int c = 0; c < (SELF ? CH : 1); ++c) selfv[c] = f4_keep(has, *reinterpret_cast<const float4*>(sp + (loff + c * 1024u)));
+  }
+  // rows without neighbours read the index of the last row that has some (in bounds) and mask its count to zero
+  const int irow = EPI != EPI_NONE ? (row < a.pool_rows ? row : a.pool_rows - 1) : row;
+  const int ilive = EPI != EPI_NONE ? (row < a.pool_rows ? -1 : 0) : -1;
+  float4 s2v[EPI == EPI_SELF2 ? CH : 1];
+  float s2w = 0.f;
+  if (EPI == EPI_SELF2) {
+    const char* sp = reinterpret_cast<const char*>(a.self2 + static_cast<int64_t>(row) * a.ld_self2);
+#pragma unroll
+    for (int c = 0; c < (EPI == EPI_SELF2 ? CH : 1); ++c) s2v[c] = *reinterpret_cast<const float4*>(sp + (loff + c * 1024u));
+    s2w = ((k_f32p)a.self2_scale)[row];
   }
   float4 tot[SHARED ? CH : 1];
 #pragma unroll
@@ -408,8 +447,8 @@ __global__ __launch_bounds__(256) void k_spmm_fast7(FastTable t, SpmmArgs a) {
     int beg[4], fin[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      beg[u] = rpp[u][row];
-      fin[u] = rep[u][row];
+      beg[u] = rpp[u][irow];
+      fin[u] = rep[u][irow];
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) asm volatile("" ::"s"(beg[u]), "s"(fin[u]));
@@ -419,7 +458,7 @@ __global__ __launch_bounds__(256) void k_spmm_fast7(FastTable t, SpmmArgs a) {
     uint64_t okm[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const int live = r0 + u < t.n_rel ? -1 : 0;   // mask, not a branch: the tail entries of the table are valid duplicates
+      const int live = (r0 + u < t.n_rel ? -1 : 0) & ilive;   // mask, not a branch: the tail entries of the table are valid duplicates
       n[u] = (fin[u] - beg[u]) & live;
       colv[u] = 0;
       if (lane < n[u]) colv[u] = cpp[u][beg[u] + lane];
@@ -589,12 +628,55 @@ __global__ __launch_bounds__(256) void k_spmm_fast7(FastTable t, SpmmArgs a) {
 #undef AGNN_OVF
 #undef AGNN_BIT
   }
-  if (SHARED) {
+  if (EPI == EPI_JOIN) {
+    // u_i = [x_i | pooled_i]: chunks 0 .. CH-1 are the self operand, CH .. 2CH-1 the pooled row; statistics, formulas and
+    // summation order are k_na_fwd<2 * CH>'s on that row
+    constexpr int NV = 2 * CH;
+    float4 v[NV];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      v[c] = selfv[SELF ? c : 0];
+      v[CH + c] = row < a.pool_rows ? tot[SHARED ? c : 0] : selfv[SELF ? c : 0];
+    }
+    char* op = reinterpret_cast<char*>(a.out + static_cast<int64_t>(row) * a.ld_out);
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      *reinterpret_cast<float4*>(op + (loff + c * 1024u)) = v[c];
+      sum += (v[c].x + v[c].y) + (v[c].z + v[c].w);
+    }
+    const float invS = 1.f / static_cast<float>(2 * a.H);
+    const float m = agnn::wave_sum_dpp(sum) * invS;
+    float q = 0.f;
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      const float dx = v[c].x - m, dy = v[c].y - m, dz = v[c].z - m, dw = v[c].w - m;
+      q += fmaf(dx, dx, dy * dy) + fmaf(dz, dz, dw * dw);     // spelled out as k_na_fwd's expression is contracted: the same bits
+    }
+    const float rs = 1.f / sqrtf(fmaf(agnn::wave_sum_dpp(q), invS, a.eps));
+    if (lane == 0) { a.mean[row] = m; a.rstd[row] = rs; }
+    char* yp = reinterpret_cast<char*>(a.y + static_cast<int64_t>(row) * a.ld_y);
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      const float4 g = reinterpret_cast<const float4*>(a.gamma)[c * 64 + lane], b = reinterpret_cast<const float4*>(a.beta)[c * 64 + lane];
+      *reinterpret_cast<float4*>(yp + (loff + c * 1024u)) =
+          make_float4(fmaf((v[c].x - m) * rs, g.x, b.x), fmaf((v[c].y - m) * rs, g.y, b.y), fmaf((v[c].z - m) * rs, g.z, b.z), fmaf((v[c].w - m) * rs, g.w, b.w));
+    }
+  } else if (SHARED) {
     char* op = reinterpret_cast<char*>(a.out + static_cast<int64_t>(row) * a.ld_out);
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       float4 o = tot[SHARED ? c : 0];
-      if (root) f4_add(o, selfv[SELF ? c : 0]);
+      if (EPI == EPI_SELF2) {
+        // the order and the roundings of the three launches this one replaces: (neighbours + rounded scaled self term) + root
+        const float4 s2 = s2v[EPI == EPI_SELF2 ? c : 0], rt = selfv[SELF ? c : 0];
+        o.x = root_plus_self2(rt.x, s2w, s2.x, o.x);
+        o.y = root_plus_self2(rt.y, s2w, s2.y, o.y);
+        o.z = root_plus_self2(rt.z, s2w, s2.z, o.z);
+        o.w = root_plus_self2(rt.w, s2w, s2.w, o.w);
+      } else if (root) {
+        f4_add(o, selfv[SELF ? c : 0]);
+      }
       *reinterpret_cast<float4*>(op + (loff + c * 1024u)) = o;
     }
   } else if (root) {
@@ -766,3 +848,104 @@ int spmm_entry(int n_rel, const agnn_rel_t* rels, int64_t n_rows, int32_t H, flo
   return check_launch("spmm");
 }
 }  // namespace
+
+// ------------------------------------------------------------------------------------------
+// The join block between the encoder and project_enc (ref: models/analysis.py:580-587 and project_enc[0]).
+// ------------------------------------------------------------------------------------------
+namespace {
+int join_check(const char* who, const agnn_rel_t* rel, int64_t n, int64_t pool_rows, int32_t H, int32_t col_limit) {
+  using namespace agnn;
+  if (H != 256 && H != 512) return fail(AGNN_EINVAL, "%s: H=%d (256 or 512: the widths the specialised kernel is built for)", who, H);
+  if (n < 0 || n >= (int64_t{1} << 31) || pool_rows < 1 || pool_rows > n || col_limit < 0) return fail(AGNN_EINVAL, "%s: n=%lld pool_rows=%lld (1 <= pool_rows <= n) col_limit=%d", who, (long long)n, (long long)pool_rows, col_limit);
+  if (!rel || !rel->rowptr || !rel->col) return fail(AGNN_EINVAL, "%s: null index", who);
+  if (rel->ew != nullptr) return fail(AGNN_EINVAL, "%s: per-edge weights are not supported", who);
+  return AGNN_OK;
+}
+
+template <int CH, bool HAS_CS, int EPI>
+void launch_join(hipStream_t stream, const agnn_rel_t& R, const SpmmArgs& a) {
+  const dim3 grid(static_cast<unsigned>(((a.n_rows + 3) / 4 + 7) & ~7));   // multiple of 8: the XCD remap is a bijection
+  FastTable f{};
+  f.n_rel = 1;
+  for (int r = 0; r < AGNN_MAX_SEG + 3; ++r) {
+    f.rowptr[r] = R.rowptr;
+    f.rowend[r] = R.rowend != nullptr ? R.rowend : R.rowptr + 1;
+    f.col[r] = R.col;
+    f.src[r] = R.src;
+    f.colscale[r] = R.colscale;
+    f.ldb[r] = static_cast<uint32_t>(R.ld_src * 4);
+  }
+  hipLaunchKernelGGL((k_spmm_fast7<CH, HAS_CS, true, true, true, EPI>), grid, dim3(256), 0, stream, f, a);
+}
+}  // namespace
+
+extern "C" int agnn_pool_cat_norm_f32(const agnn_rel_t* rel, const float* x, int64_t ld_x, int64_t n, int64_t pool_rows, int32_t H,
+                                      int32_t col_limit, const float* gamma, const float* beta, float eps, float* u, int64_t ld_u,
+                                      float* y, int64_t ld_y, float* mean, float* rstd, float* inv_cnt, agnn_stream_t stream_) {
+  using namespace agnn;
+  if (n == 0) return AGNN_OK;
+  if (int rc = join_check("pool_cat_norm", rel, n, pool_rows, H, col_limit)) return rc;
+  if (!x || !gamma || !beta || !u || !y || !mean || !rstd) return fail(AGNN_EINVAL, "pool_cat_norm: null argument");
+  if (!aligned16(x) || !aligned16(gamma) || !aligned16(beta) || !aligned16(u) || !aligned16(y) || (ld_x & 3) || (ld_u & 3) || (ld_y & 3) ||
+      ld_x < H || ld_u < 2 * H || ld_y < 2 * H || ld_x >= (int64_t{1} << 30))
+    return fail(AGNN_EALIGN, "pool_cat_norm: operands must be 16-byte aligned; ld_x >= H, ld_u and ld_y >= 2H, multiples of 4");
+  agnn_rel_t R = *rel;
+  R.src = x;
+  R.ld_src = ld_x;
+  R.colscale = nullptr;
+  SpmmArgs a{};
+  a.n_rows = static_cast<int32_t>(n);
+  a.H = H;
+  a.out = u;
+  a.ld_out = ld_u;
+  a.self = x;
+  a.ld_self = ld_x;
+  a.inv_cnt = inv_cnt;
+  a.col_limit = col_limit;
+  a.flags = AGNN_SPMM_MEAN | AGNN_SPMM_SKIP_SELF;
+  a.self_rows = a.n_rows;
+  a.pool_rows = static_cast<int32_t>(pool_rows);
+  a.eps = eps;
+  a.gamma = gamma;
+  a.beta = beta;
+  a.y = y;
+  a.ld_y = ld_y;
+  a.mean = mean;
+  a.rstd = rstd;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (H == 256) launch_join<1, false, EPI_JOIN>(stream, R, a);
+  else launch_join<2, false, EPI_JOIN>(stream, R, a);
+  return check_launch("pool_cat_norm");
+}
+
+extern "C" int agnn_pool_cat_bwd_f32(const agnn_rel_t* rel_t, const float* du, int64_t ld_du, const float* inv_cnt, int64_t n,
+                                     int64_t pool_rows, int32_t H, float* dx, int64_t ld_dx, agnn_stream_t stream_) {
+  using namespace agnn;
+  if (n == 0) return AGNN_OK;
+  if (int rc = join_check("pool_cat_bwd", rel_t, n, pool_rows, H, 0)) return rc;
+  if (!du || !inv_cnt || !dx) return fail(AGNN_EINVAL, "pool_cat_bwd: null argument");
+  if (!aligned16(du) || !aligned16(dx) || (ld_du & 3) || (ld_dx & 3) || ld_du < 2 * H || ld_dx < H || ld_du >= (int64_t{1} << 30))
+    return fail(AGNN_EALIGN, "pool_cat_bwd: operands must be 16-byte aligned; ld_du >= 2H, ld_dx >= H, multiples of 4");
+  agnn_rel_t R = *rel_t;
+  R.src = du + H;             // the pooled half of every row
+  R.ld_src = ld_du;
+  R.colscale = inv_cnt;       // 1 / count of the destination
+  SpmmArgs a{};
+  a.n_rows = static_cast<int32_t>(n);
+  a.H = H;
+  a.out = dx;
+  a.ld_out = ld_dx;
+  a.self = du;                // the x half: the cat's own gradient (the root operand)
+  a.ld_self = ld_du;
+  a.col_limit = static_cast<int32_t>(pool_rows);       // destinations the forward never computed take no part
+  a.flags = AGNN_SPMM_SKIP_SELF | AGNN_SPMM_ROOT;
+  a.self_rows = a.n_rows;
+  a.pool_rows = static_cast<int32_t>(pool_rows);
+  a.self2 = du + H;
+  a.ld_self2 = ld_du;
+  a.self2_scale = inv_cnt;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (H == 256) launch_join<1, true, EPI_SELF2>(stream, R, a);
+  else launch_join<2, true, EPI_SELF2>(stream, R, a);
+  return check_launch("pool_cat_bwd");
+}

@@ -35,7 +35,7 @@ from . import _lib, ops, resident
 from .gru import gru_forward
 from .fused import FusedSequential, norm_act
 from .params import sage_operands, sage_operands_cat
-from .linear import Linear, deferring, flush_deferred, linear, set_home_stream
+from .linear import Linear, deferring, flush_deferred, linear, linear2, set_home_stream
 from .core_layers import JumpingKnowledge
 from .graph import HeteroIndex, hetero_index
 
@@ -263,6 +263,7 @@ def _side_stream(dev: torch.device) -> "torch.cuda.Stream":
 SIDE_STREAM_PRIORITY = 0        # A/B switch (bench.py --side-priority): -1 = the sequence branch's stream ahead of the main one
 
 
+CAT_PROJ_TWO_OPERANDS = True    # cat_proj reads the GNN stack's and the sequence branch's outputs where they lie (linear.linear2); False: torch.cat first
 LATE_SEQUENCE_BACKWARD = True   # the sequence branch behind a late-created node (_LateNode); bench.py --schedule measures both
 
 
@@ -476,7 +477,10 @@ class _HybridMixin:
         if side is not None:
             torch.cuda.current_stream(x.device).wait_stream(side)
             z.record_stream(torch.cuda.current_stream(x.device))
-        return _stamped(self.cat_proj(torch.cat((x, z), dim=-1)), "cat_proj")
+        y = linear2(x, z, self.cat_proj.weight, self.cat_proj.bias) if CAT_PROJ_TWO_OPERANDS else None
+        if y is None:                                    # fewer rows or other widths than the hand-written kernel takes
+            y = self.cat_proj(torch.cat((x, z), dim=-1))
+        return _stamped(y, "cat_proj")
 
 
 class HybridGNN(nn.Module, _HybridMixin):

@@ -165,11 +165,18 @@ def skip_act(o: torch.Tensor, x: Optional[torch.Tensor], skip: Optional[torch.Te
 
 
 def norm_act(x: torch.Tensor, ln: nn.LayerNorm, pre_relu: bool = False, post_relu: bool = False, p: float = 0.0,
-             training: bool = False) -> torch.Tensor:
-    """dropout_p( relu?( LayerNorm( relu?(x) ) ) ) on the last dimension of x (2-D or 3-D, fp32, H % 4 == 0)."""
+             training: bool = False, pre=None) -> torch.Tensor:
+    """dropout_p( relu?( LayerNorm( relu?(x) ) ) ) on the last dimension of x (2-D or 3-D, fp32, H % 4 == 0).
+    `pre` = [y, mean, rstd]: a plain LayerNorm (no ReLU, no dropout) that x's producer has already applied."""
     H = x.shape[-1]
     usable = (ENABLED and x.is_cuda and x.dtype == torch.float32 and H % 4 == 0 and H <= 1024 and ln.elementwise_affine
               and tuple(ln.normalized_shape) == (H,))
+    if pre is not None:
+        if not usable or pre_relu or post_relu or (p > 0 and training) or x.dim() != 2:
+            raise _lib.AgnnError("norm_act: precomputed results stand for a plain LayerNorm on the kernel path")
+        if not (torch.is_grad_enabled() and (x.requires_grad or ln.weight.requires_grad or ln.bias.requires_grad)):
+            return pre[0]
+        return _NormAct.apply(x, ln.weight, ln.bias, ln.eps, 0.0, 0, next(_CALL_IDS) & 0xFFFFFFFF, 0, False, None, pre)
     if not usable:
         y = F.relu(x) if pre_relu else x
         y = ln(y)
@@ -203,9 +210,16 @@ class FusedSequential(nn.Sequential):
     """`nn.Sequential` whose forward runs `ReLU -> LayerNorm [-> Dropout]`, `LayerNorm [-> ReLU] [-> Dropout]` chains
     through `norm_act`; every other module runs as usual.  Module indices (and so `state_dict` keys) are untouched."""
 
-    def forward(self, x):
+    def forward(self, x, pre=None):
+        """`pre` = [y, mean, rstd]: the first module, a LayerNorm with neither ReLU nor dropout behind it, has been applied by x's
+        producer (models.pool_cat_norm); it only takes its place in the autograd graph."""
         mods = list(self)
         i = 0
+        if pre is not None:
+            if not mods or not isinstance(mods[0], nn.LayerNorm) or (len(mods) > 1 and isinstance(mods[1], (nn.ReLU, nn.Dropout))):
+                raise _lib.AgnnError("FusedSequential: precomputed results need a leading plain LayerNorm")
+            x = norm_act(x, mods[0], pre=pre)
+            i = 1
         while i < len(mods):
             m = mods[i]
             nxt = mods[i + 1] if i + 1 < len(mods) else None

@@ -239,10 +239,10 @@ def _spill(fns, keep: float, other) -> list:
     flush until only `keep` of the list's FLOPs remain; returns what stays.  The operands are complete on the current stream now:
     an event recorded here orders `other` behind them.  Work that was itself handed over from another stream (`event` set, or a
     `defer_home` wrapper) stays where it was sent: `other` may be the stream it waits for."""
-    cost = lambda f: 2.0 * f.dy.shape[0] * f.dy.shape[1] * f.x.shape[1]                 # noqa: E731
-    units, cur = [], []                  # [leading closures], [product, its closures ...], ...
+    cost = lambda u: sum(2.0 * f.dy.shape[0] * f.dy.shape[1] * f.x.shape[1] for f in u if isinstance(f, WgItem))       # noqa: E731
+    units, cur = [], []                  # [leading closures], [product (one item, or its two column blocks), its closures ...], ...
     for f in fns:
-        if isinstance(f, WgItem):
+        if isinstance(f, WgItem) and not (f.follows and cur and isinstance(cur[-1], WgItem) and cur[-1].dy is f.dy):
             units.append(cur)
             cur = [f]
         else:
@@ -250,7 +250,7 @@ def _spill(fns, keep: float, other) -> list:
     units.append(cur)
     movable = lambda u: (u and isinstance(u[0], WgItem) and u[0].event is None                                  # noqa: E731
                          and not any(getattr(f, "event", None) is not None or getattr(f, "handed_over", False) for f in u[1:]))
-    total = sum(cost(u[0]) for u in units if u and isinstance(u[0], WgItem))
+    total = sum(cost(u) for u in units if u and isinstance(u[0], WgItem))
     if total <= 0:
         return fns
     moved, out = 0.0, set()
@@ -258,9 +258,9 @@ def _spill(fns, keep: float, other) -> list:
         u = units[i]
         if not movable(u):
             continue
-        if moved + cost(u[0]) > (1.0 - keep) * total + 1e-9:
+        if moved + cost(u) > (1.0 - keep) * total + 1e-9:
             break
-        moved += cost(u[0])
+        moved += cost(u)
         out.add(i)
     if not out:
         return fns
@@ -322,13 +322,19 @@ def _ok(t: torch.Tensor) -> bool:
             and t.shape[1] % 2 == 0 and t.data_ptr() % 8 == 0)
 
 
+def _dw_ok(dw: torch.Tensor) -> bool:
+    """A weight-gradient destination: a contiguous matrix, or a column block of one (`agnn_wgrad_item_t.ld_dw`)."""
+    return dw.dim() == 2 and dw.stride(1) == 1 and dw.stride(0) >= dw.shape[1] and dw.stride(0) % 2 == 0 and dw.data_ptr() % 8 == 0
+
+
 def weight_grad(dy: torch.Tensor, x: torch.Tensor, want_bias: bool, dw_out: Optional[torch.Tensor] = None,
                 db_out: Optional[torch.Tensor] = None):
     """(dW [out, in], db [out] or None) for dy [N, out], x [N, in] on the HIP kernel; library GEMM when the
     shape / alignment does not fit the kernel.  An odd `in` is served when x has a spare (zero) column behind its last
     one — rows padded to an even stride, as models.encode lays out the 153-wide note input: the kernel then runs on
-    in + 1 columns and the extra gradient column is dropped.  `dw_out` [out, in] / `db_out` [out] (contiguous, even `in`):
-    write the results there (a slot of a stacked gradient) instead of into fresh tensors."""
+    in + 1 columns and the extra gradient column is dropped.  `dw_out` [out, in] / `db_out` [out] (even `in`; `dw_out` contiguous
+    or a column block of a wider contiguous matrix): write the results there (a slot of a stacked gradient, one operand's
+    block of `linear2`'s weight gradient) instead of into fresh tensors."""
     n, out_f = dy.shape
     in_f = x.shape[1]
     in_k = in_f
@@ -347,8 +353,8 @@ def weight_grad(dy: torch.Tensor, x: torch.Tensor, want_bias: bool, dw_out: Opti
     lib = _lib.load()
     dev = dy.device
     if dw_out is not None:
-        if in_k != in_f or tuple(dw_out.shape) != (out_f, in_f) or not dw_out.is_contiguous() or (want_bias and (db_out is None or not db_out.is_contiguous())):
-            raise _lib.AgnnError("weight_grad: dw_out / db_out must be contiguous [out, in] / [out] with an even `in`")
+        if in_k != in_f or tuple(dw_out.shape) != (out_f, in_f) or not _dw_ok(dw_out) or (want_bias and (db_out is None or not db_out.is_contiguous())):
+            raise _lib.AgnnError("weight_grad: dw_out / db_out must be [out, in] (rows contiguous, even stride) / contiguous [out] with an even `in`")
         dw, db = dw_out, (db_out if want_bias else None)
     else:
         dw = torch.empty((out_f, in_k), dtype=torch.float32, device=dev)
@@ -365,10 +371,13 @@ def weight_grad(dy: torch.Tensor, x: torch.Tensor, want_bias: bool, dw_out: Opti
 class WgItem:
     """One pending weight-gradient product dW = dY^T X (+ db) with its destinations: what a projection's backward leaves behind
     under dp.defer_weight_grads instead of a closure, so that the flush can issue all of them in one launch pair."""
-    __slots__ = ("dy", "x", "want_bias", "dw_out", "db_out", "event")
+    __slots__ = ("dy", "x", "want_bias", "dw_out", "db_out", "event", "follows")
 
-    def __init__(self, dy, x, want_bias, dw_out, db_out):
+    def __init__(self, dy, x, want_bias, dw_out, db_out, follows=False):
+        """`follows`: the second column block of the product whose first block is the item before it (`linear2`): the two count as
+        ONE product when groups are formed, so the launches are cut where they were cut with the input concatenated."""
         self.dy, self.x, self.want_bias, self.dw_out, self.db_out, self.event = dy, x, bool(want_bias), dw_out, db_out, None
+        self.follows = bool(follows)
 
     def tensors(self):
         return (self.dy, self.x, self.dw_out, self.db_out)
@@ -412,16 +421,19 @@ BATCH = True             # A/B switch for benchmarking: False = one launch pair 
 
 def weight_grad_batch(items) -> None:
     """`WgItem`s in as few launches as possible: those the MFMA kernel takes (fp32, even widths, >= MIN_ROWS rows, output up to
-    MAX_OUT_IN, results written in place) go to `agnn_wgrad_batch_f32` in groups of up to 16, the rest one by one."""
+    MAX_OUT_IN, results written in place) go to `agnn_wgrad_batch_f32` in groups of up to 16 products, the rest one by one.  A
+    product in two column blocks (`WgItem.follows`) is two items of the launch and one product of the count: the groups, and with
+    them every item's row slices, are those of the same list with that product's input concatenated."""
     lib = None
     group = []
+    products = 0
 
     def fits(it):
         n, out_f = it.dy.shape
         in_f = it.x.shape[1]
         return (BATCH and ENABLED and it.dy.is_cuda and it.dy.dim() == 2 and it.x.dim() == 2 and n >= MIN_ROWS and out_f * in_f <= MAX_OUT_IN and in_f % 2 == 0
-                and _ok(it.dy) and _ok(it.x) and it.dw_out is not None and tuple(it.dw_out.shape) == (out_f, in_f) and it.dw_out.is_contiguous()
-                and it.dw_out.data_ptr() % 8 == 0 and (not it.want_bias or (it.db_out is not None and it.db_out.is_contiguous() and it.db_out.data_ptr() % 8 == 0)))
+                and _ok(it.dy) and _ok(it.x) and it.dw_out is not None and tuple(it.dw_out.shape) == (out_f, in_f) and _dw_ok(it.dw_out)
+                and (not it.want_bias or (it.db_out is not None and it.db_out.is_contiguous() and it.db_out.data_ptr() % 8 == 0)))
 
     def run(group):
         if len(group) == 1:
@@ -442,10 +454,12 @@ def weight_grad_batch(items) -> None:
 
     for it in items:
         if fits(it):
-            group.append(it)
-            if len(group) == _lib.WGRAD_BATCH_MAX:
+            joins = it.follows and group and group[-1].dy is it.dy
+            if group and ((products == _lib.WGRAD_BATCH_MAX and not joins) or len(group) == _lib.WGRAD_BATCH_MAX_ITEMS):
                 run(group)
-                group = []
+                group, products, joins = [], 0, False
+            group.append(it)
+            products += 0 if joins else 1
         else:
             it()
     if group:
@@ -560,6 +574,79 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, a
             return _LinearFn.apply(x.reshape(-1, x.shape[-1]), w, b, None).view(x.shape[0], x.shape[1], -1)
     y = F.linear(x, w, b)
     return y + acc if acc is not None else y
+
+
+def _hand_gemm2_ok(x0, x1, w, b) -> bool:
+    """`_hand_gemm_ok` for the product on [x0 | x1]: the sizes of the concatenation, the layout of each block."""
+    k0, k1 = x0.shape[1], x1.shape[1]
+    blk = lambda t: (t.is_cuda and t.dim() == 2 and t.dtype == torch.float32 and t.shape[1] % 16 == 0 and t.shape[1] > 0 and t.stride(1) == 1       # noqa: E731
+                     and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0)
+    return (blk(x0) and blk(x1) and x0.shape[0] == x1.shape[0] and x0.shape[0] >= HAND_GEMM_MIN_ROWS and w.dtype == torch.float32 and w.dim() == 2
+            and w.shape[1] == k0 + k1 and HAND_GEMM_MIN_K <= k0 + k1 <= HAND_GEMM_MAX_K and w.shape[0] >= HAND_GEMM_MIN_N and w.shape[0] % 64 == 0
+            and w.stride(1) == 1 and w.stride(0) % 4 == 0 and w.stride(0) >= w.shape[1] and w.data_ptr() % 16 == 0
+            and (b is None or (b.dtype == torch.float32 and b.is_contiguous())))
+
+
+def hand_gemm2(x0: torch.Tensor, x1: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
+    """[x0 | x1] W^T (+ b) without the concatenation (csrc/gemm.hip, agnn_gemm_nt2_f32); operands as `_hand_gemm2_ok` checks."""
+    y = torch.empty((x0.shape[0], w.shape[0]), dtype=torch.float32, device=x0.device)
+    _lib.check(_lib.load().agnn_gemm_nt2_f32(x0.data_ptr(), x0.stride(0), x0.shape[1], x1.data_ptr(), x1.stride(0), x1.shape[1], w.data_ptr(),
+                                             w.stride(0), _lib.ptr(b), x0.shape[0], w.shape[0], y.data_ptr(), y.stride(0),
+                                             _lib.stream_ptr(x0.device)), "agnn_gemm_nt2_f32")
+    return y
+
+
+class _Linear2Fn(torch.autograd.Function):
+    """`_LinearFn` on an input that stays in two column blocks: the input gradient is one library product whose halves go out
+    as views, the weight gradient two products that write column blocks of the one dW (the bias gradient goes with the first)."""
+
+    @staticmethod
+    def forward(ctx, x0, x1, w, b):
+        ctx.save_for_backward(x0, x1, w)
+        ctx.has_bias = b is not None
+        ctx.wg_async = _async_ok(w) and _async_ok(b)
+        ctx.wg_defer = _deferrable(w) and _deferrable(b)
+        ctx.steal_refs = leaf_refs(w, b)
+        ctx.set_materialize_grads(False)
+        return hand_gemm2(x0, x1, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return None, None, None, None
+        x0, x1, w = ctx.saved_tensors
+        k0 = x0.shape[1]
+        dw = db = None
+        want_w = ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3])
+        want_b = ctx.has_bias and ctx.needs_input_grad[3]
+        steals = ctx.wg_async and all_steal(ctx.steal_refs)
+        if want_w:
+            dw = torch.empty((dy.shape[1], w.shape[1]), dtype=torch.float32, device=dy.device)
+            db = torch.empty((dy.shape[1],), dtype=torch.float32, device=dy.device) if want_b else None
+            dw_k, db_k = dw.detach(), (db.detach() if db is not None else None)       # aliases: see _LinearFn.backward
+            if steals and ctx.wg_defer and deferring(dy):
+                defer(WgItem(dy, x0, want_b, dw_k[:, :k0], db_k), dy.device)
+                defer(WgItem(dy, x1, False, dw_k[:, k0:], None, follows=True), dy.device)
+            else:
+                with wgrad_stream(dy.device, dy, x0, x1, active=steals):
+                    weight_grad(dy, x0, want_b, dw_out=dw_k[:, :k0], db_out=db_k)
+                    weight_grad(dy, x1, False, dw_out=dw_k[:, k0:])
+        dx0 = dx1 = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            dx = dy @ w
+            dx0 = dx[:, :k0] if ctx.needs_input_grad[0] else None
+            dx1 = dx[:, k0:] if ctx.needs_input_grad[1] else None
+        return dx0, dx1, dw, db
+
+
+def linear2(x0: torch.Tensor, x1: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """cat((x0, x1), -1) W^T (+ b) with the two blocks left where their producers wrote them, or None when the operands are
+    not the hand-written kernel's (`_hand_gemm2_ok`): the caller then concatenates and calls `linear`."""
+    if not (HAND_GEMM and _hand_gemm2_ok(x0, x1, w, b)):
+        return None
+    if torch.is_grad_enabled() and (x0.requires_grad or x1.requires_grad or w.requires_grad or (b is not None and b.requires_grad)):
+        return _Linear2Fn.apply(x0, x1, w, b)
+    return hand_gemm2(x0, x1, w, b)
 
 
 class Linear(nn.Linear):

@@ -13,11 +13,77 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .encoders import HybridGNN, MetricalGNN
-from .fused import FusedSequential, advance_rng
+from .fused import FusedSequential, _al16, advance_rng
 from .embedding import embed_cat
 from .heads import CrossTaskTransformer, fused_head_logits, fused_logit_fusion
 from .linear import Linear
 from .graph import SegSpec, build_csr
+
+
+JOIN_FUSED = True        # onset pooling + its cat + project_enc's first LayerNorm in one launch each way (agnn_pool_cat_norm_f32); False: three
+
+
+def _onset_index(n: int, onset_edges: torch.Tensor, batch_size: int, index):
+    """The onset relation's by-source CSR and its transpose: the encoder's batch index when it is at hand, else built here."""
+    et = ("note", "onset", "note")
+    if index is not None and et in index.bwd and index.bwd[et].n_rows >= n:
+        return index.bwd[et], index.fwd[et]
+    fwd, bwd = build_csr([SegSpec(onset_edges[0], onset_edges[1], n_rows=max(n, batch_size)),
+                          SegSpec(onset_edges[1], onset_edges[0], n_rows=max(n, batch_size))])
+    return fwd, bwd
+
+
+class _PoolCat(torch.autograd.Function):
+    """u = cat([x, onset_pool(x)]) written by the pooling kernel itself, which also leaves LayerNorm(u) and its statistics in
+    `box` for the consumer (`FusedSequential(..., pre=box)`: fused._NormAct then only carries the LayerNorm's backward).  Backward:
+    the cat's, the self term's and the neighbour term's gradients of x in one launch on du."""
+
+    @staticmethod
+    def forward(ctx, x, fwd, bwd, n_pool, col_limit, gamma, beta, eps, box):
+        dev = x.device
+        lib = _lib.load()
+        n, H = x.shape
+        u = torch.empty((n, 2 * H), dtype=torch.float32, device=dev)
+        y = torch.empty((n, 2 * H), dtype=torch.float32, device=dev)
+        mean = torch.empty((n,), dtype=torch.float32, device=dev)
+        rstd = torch.empty((n,), dtype=torch.float32, device=dev)
+        inv_cnt = torch.empty((n,), dtype=torch.float32, device=dev)
+        rel = _lib.make_rels([dict(src=None, rowptr=fwd.rowptr.data_ptr(), col=fwd.col.data_ptr(), ld_src=0)])
+        _lib.check(lib.agnn_pool_cat_norm_f32(rel, x.data_ptr(), x.stride(0), n, n_pool, H, min(int(col_limit), _lib.INT32_MAX), gamma.data_ptr(),
+                                              beta.data_ptr(), float(eps), u.data_ptr(), u.stride(0), y.data_ptr(), y.stride(0), mean.data_ptr(),
+                                              rstd.data_ptr(), inv_cnt.data_ptr(), _lib.stream_ptr(dev)), "agnn_pool_cat_norm_f32")
+        box.extend([y, mean, rstd])
+        ctx.bwd, ctx.n_pool = bwd, n_pool
+        ctx.save_for_backward(inv_cnt)
+        return u
+
+    @staticmethod
+    def backward(ctx, du):
+        inv_cnt, = ctx.saved_tensors
+        du = du if ops._view_ok(du) else _lib.f32c(du)
+        n, H = du.shape[0], du.shape[1] // 2
+        dx = torch.empty((n, H), dtype=torch.float32, device=du.device)
+        rel = _lib.make_rels([dict(src=None, rowptr=ctx.bwd.rowptr.data_ptr(), col=ctx.bwd.col.data_ptr(), ld_src=0)])
+        _lib.check(_lib.load().agnn_pool_cat_bwd_f32(rel, du.data_ptr(), du.stride(0), inv_cnt.data_ptr(), n, ctx.n_pool, H, dx.data_ptr(),
+                                                     dx.stride(0), _lib.stream_ptr(du.device)), "agnn_pool_cat_bwd_f32")
+        return dx, None, None, None, None, None, None, None, None
+
+
+def pool_cat_norm(x: torch.Tensor, onset_edges: torch.Tensor, batch_size: int, ln: nn.LayerNorm, index=None):
+    """(u, [y, mean, rstd]) with u = onset_pool(x, ...) and y = ln(u) from one launch, or None when the shapes are not the fused
+    kernel's (H = 256 or 512, fp32 rows the kernel can read, at least one pooled row): the caller keeps the three launches."""
+    n, H = int(x.shape[0]), int(x.shape[1])
+    n_pool = min(n, int(batch_size))
+    if not (x.is_cuda and x.dim() == 2 and H in ops.ROOT_WIDTHS and n_pool >= 1 and ops._view_ok(x) and x.stride(0) >= H and ln.elementwise_affine
+            and tuple(ln.normalized_shape) == (2 * H,) and ln.weight.dtype == torch.float32):
+        return None
+    fwd, bwd = _onset_index(n, onset_edges, batch_size, index)
+    if fwd.n_rows < n_pool or bwd.n_rows < n_pool:
+        return None
+    gamma, beta = _al16(ln.weight.detach().contiguous()), _al16(ln.bias.detach().contiguous())
+    box: list = []
+    u = _PoolCat.apply(x, fwd, bwd, n_pool, min(int(batch_size), n), gamma, beta, ln.eps, box)     # (sources are rows of x)
+    return u, box
 
 
 def onset_pool(x: torch.Tensor, onset_edges: torch.Tensor, batch_size: int, index=None) -> torch.Tensor:
@@ -28,12 +94,7 @@ def onset_pool(x: torch.Tensor, onset_edges: torch.Tensor, batch_size: int, inde
     (`index`), that CSR and its transpose are reused instead of built again."""
     _lib.require_gpu(x, onset_edges)
     n = int(x.shape[0])
-    et = ("note", "onset", "note")
-    if index is not None and et in index.bwd and index.bwd[et].n_rows >= n:
-        fwd, bwd = index.bwd[et], index.fwd[et]
-    else:
-        fwd, bwd = build_csr([SegSpec(onset_edges[0], onset_edges[1], n_rows=max(n, batch_size)),
-                              SegSpec(onset_edges[1], onset_edges[0], n_rows=max(n, batch_size))])
+    fwd, bwd = _onset_index(n, onset_edges, batch_size, index)
     spec = ops.AggSpec(fwd=[fwd], bwd=[bwd], src_id=[0], n_rows=min(n, batch_size), mean=True, shared_slot=True,
                        skip_self=True, col_limit=batch_size)
     pooled = ops.aggregate(spec, [x], self_t=x)
@@ -152,8 +213,11 @@ class TorchAnalysisGNN(nn.Module):
                          batch_size=batch_size, neighbor_mask_node=neighbor_mask_node,
                          neighbor_mask_edge=neighbor_mask_edge, return_edge_index=False, edge_attr_dict=None)
         index = getattr(getattr(self.encoder, "gnn", None), "last_index", None)    # the CSR the encoder just built
-        x = onset_pool(x, edge_index_dict[("note", "onset", "note")], batch_size, index)
-        return self.project_enc(x)
+        onset = edge_index_dict[("note", "onset", "note")]
+        joined = pool_cat_norm(x, onset, batch_size, self.project_enc[0], index) if JOIN_FUSED and x.is_cuda else None
+        if joined is not None:
+            return self.project_enc(joined[0], pre=joined[1])
+        return self.project_enc(onset_pool(x, onset, batch_size, index))
 
     @torch._dynamo.disable
     def forward_clf(self, x, tasks=None):

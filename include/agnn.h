@@ -184,6 +184,25 @@ int agnn_spmm_self_grad_f32(const float* dout, int64_t ld_dout, int64_t rel_stri
                             int64_t ld_inv, int64_t n_rows, int32_t H, float* out, int64_t ld_out, int32_t accumulate,
                             agnn_stream_t stream);
 
+/* The join block between the encoder and the wrapper's project_enc (ref: models/analysis.py:580-587 followed by project_enc[0] =
+ * LayerNorm(2H)): the onset pooling writes its own concatenation and normalises it, one wave per row, one launch.  For i < n:
+ *     pooled_i = i < pool_rows ? (x_i + sum_{valid p in row i} x[col[p]]) / max(cnt_i, 1) : x_i
+ *                (valid(p) = col != i && col < col_limit; exactly agnn_spmm_f32's MEAN | SKIP_SELF result with self = x, shared slot)
+ *     u_i      = [x_i | pooled_i]                     -> u [n, 2H]   (what the LayerNorm's backward reads)
+ *     y_i      = LayerNorm_eps(u_i) * gamma + beta    -> y [n, 2H],  mean [n], rstd [n]  (as agnn_norm_act_fwd_f32, no flags)
+ *     inv_cnt[i] = 1 / max(cnt_i, 1)                  (optional; 1 for i >= pool_rows)
+ * `rel`: rowptr / col (/ rowend) of the by-destination index with at least pool_rows rows; its src, ld_src, ew, colscale are
+ * ignored (ew must be NULL).  H = 256 or 512; 1 <= pool_rows <= n. */
+int agnn_pool_cat_norm_f32(const agnn_rel_t* rel /* (host) */, const float* x, int64_t ld_x, int64_t n, int64_t pool_rows, int32_t H,
+                           int32_t col_limit, const float* gamma, const float* beta, float eps, float* u, int64_t ld_u,
+                           float* y, int64_t ld_y, float* mean, float* rstd, float* inv_cnt, agnn_stream_t stream);
+/* Its backward behind the LayerNorm's (du [n, 2H] from agnn_norm_act_bwd_f32), one launch:
+ *     dx_i = du[i, 0:H] + inv_cnt[i] * du[i, H:2H] + sum_{valid p in row i of rel_t} inv_cnt[col[p]] * du[col[p], H:2H]
+ * `rel_t`: the transposed (by-source) index, at least pool_rows rows; valid(p) = col != i && col < pool_rows; rows at or beyond
+ * pool_rows have no neighbour term. */
+int agnn_pool_cat_bwd_f32(const agnn_rel_t* rel_t /* (host) */, const float* du, int64_t ld_du, const float* inv_cnt, int64_t n,
+                          int64_t pool_rows, int32_t H, float* dx, int64_t ld_dx, agnn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Persistent bidirectional GRU layer (one launch for all T steps), replacing `torch.nn.GRU` in the
  * hybrid branch (ref: models/cadence.py:249-285, models/analysis.py:527-537).  hidden must be 128
@@ -325,6 +344,11 @@ int agnn_gemm_nn_f32(const float* a, int64_t ld_a, const float* w /* [K, N] */, 
                      int32_t K, float* c, int64_t ld_c, agnn_stream_t stream);
 int agnn_gemm_nt_f32(const float* a, int64_t ld_a, const float* w, int64_t ld_w, const float* bias, int64_t M, int32_t N,
                      int32_t K, float* c, int64_t ld_c, agnn_stream_t stream);
+/* agnn_gemm_nt_f32 with its first operand in two column blocks that are never concatenated:  C = [a0 | a1] * w^T (+ bias), a0 [M, K0] and
+ * a1 [M, K1] with their own leading dimensions, w [N, K0 + K1].  K0 and K1 multiples of 16 (the tile's k-step); same k order, so the
+ * result has the bits of agnn_gemm_nt_f32 on the concatenation. */
+int agnn_gemm_nt2_f32(const float* a0, int64_t ld_a0, int32_t K0, const float* a1, int64_t ld_a1, int32_t K1, const float* w,
+                      int64_t ld_w, const float* bias, int64_t M, int32_t N, float* c, int64_t ld_c, agnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Aggregation side of the in-tree RelEdgeConv (ref: models/core/gnn.py:99-105: m_ij = W_e [h_j || |h_i - h_j|] + b_e scattered
@@ -414,7 +438,9 @@ int agnn_wgrad_f32(const float* dy, int64_t ld_dy, const float* x, int64_t ld_x,
 /* Several weight gradients in ONE launch pair (product kernel + slab reduction): the items' workgroups fill the chip together, so
  * every item gets by with a few row slices instead of up to 64 (fewer slabs written and read back, longer K loops) and the
  * step's ~20 reduction launches become one per group.  Same arithmetic per item as agnn_wgrad_f32 with that slice count
- * (deterministic; the slice count — hence the summation order — depends on the group's composition).  At most 16 items. */
+ * (deterministic; the slice count — hence the summation order — depends on the group's composition).  At most 24 items: the host
+ * groups 16 products, and a product whose input lies in two column blocks comes as two items (same tiles, same slices, same bits
+ * as the one item on the concatenation when the blocks are multiples of the 128-column tile). */
 typedef struct {
   const float* dy;   /* (device) [n, out_f], leading dimension ld_dy */
   const float* x;    /* (device) [n, in_f],  leading dimension ld_x  */
