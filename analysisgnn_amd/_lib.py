@@ -99,6 +99,23 @@ class PackItem(C.Structure):
                 ("rows", C.c_int32), ("cols", C.c_int32), ("n_src", C.c_int32), ("vec_ok", C.c_int32)]
 
 
+PACK_MAX_ITEMS = 24
+GRAD_MAX_SUMS = 16            # AGNN_GRAD_MAX_SUMS: column sums per agnn_grad_epilogue_f32 call
+
+
+class GatherItem(C.Structure):
+    _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("n", C.c_int64)]
+
+
+class GradDst(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("ld", C.c_int64), ("c0", C.c_int32), ("c1", C.c_int32)]
+
+
+class GradItem(C.Structure):
+    _fields_ = [("dy", C.c_void_p), ("x", C.c_void_p), ("ld_dy", C.c_int64), ("ld_x", C.c_int64), ("n", C.c_int64), ("out_f", C.c_int32),
+                ("in_f", C.c_int32), ("n_dw", C.c_int32), ("n_db", C.c_int32), ("dw", GradDst * PACK_MAX_SRC), ("db", C.c_void_p * PACK_MAX_SRC)]
+
+
 LR_CONSTANT, LR_WARMUP_COSINE, LR_WARMUP_EXP = 0, 1, 2
 
 
@@ -159,6 +176,8 @@ SIGNATURES = {
                                   C.c_void_p]),
     "agnn_wgrad_batch_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(WgradItem)]),
     "agnn_wgrad_batch_f32": (C.c_int, [C.c_int32, C.POINTER(WgradItem), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "agnn_grad_epilogue_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(GradItem)]),
+    "agnn_grad_epilogue_f32": (C.c_int, [C.c_int32, C.POINTER(GradItem), C.c_int32, C.POINTER(ColsumItem), C.c_void_p, C.c_size_t, C.c_void_p]),
     "agnn_gemm_nt_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                    C.c_int64, C.c_void_p]),
     "agnn_gemm_nn_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
@@ -196,6 +215,7 @@ SIGNATURES = {
     "agnn_wgrad_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "agnn_pack_f32": (C.c_int, [C.c_int32, C.POINTER(PackItem), C.c_void_p]),
+    "agnn_gather_f32": (C.c_int, [C.c_int32, C.POINTER(GatherItem), C.c_void_p]),
     "agnn_debug_stamp": (C.c_int, [C.c_void_p, C.c_void_p]),
     "agnn_gproj_fwd_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -93,6 +93,78 @@ extern "C" int agnn_pack_f32(int32_t n_items, const agnn_pack_item_t* items, agn
   return AGNN_OK;
 }
 
+// ---- plain gather: up to AGNN_GATHER_MAX_ITEMS contiguous pieces copied or cleared per launch -------------------------------------
+namespace {
+
+struct GatherTable {
+  float* dst[AGNN_GATHER_MAX_ITEMS];
+  const float* src[AGNN_GATHER_MAX_ITEMS];            // nullptr: zero-fill
+  int32_t n[AGNN_GATHER_MAX_ITEMS];
+  int32_t first_block[AGNN_GATHER_MAX_ITEMS + 1];     // a block = 256 threads x 4 steps x 4 floats
+  int32_t count;
+};
+static_assert(sizeof(GatherTable) <= 4096, "GatherTable travels as a kernel argument");
+
+__global__ __launch_bounds__(256) void k_gather(GatherTable t) {
+  int lo = 0, hi = t.count - 1;                       // the item of this block: binary search over the prefix table (uniform)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (static_cast<int>(blockIdx.x) >= t.first_block[mid]) lo = mid; else hi = mid - 1;
+  }
+  float* dst = t.dst[lo];
+  const float* src = t.src[lo];
+  const int n = t.n[lo];
+  const bool vec = ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) == 0;     // (a null source is aligned)
+  const int base = (static_cast<int>(blockIdx.x) - t.first_block[lo]) * (kElemsPerBlock / 4);            // in float4 units
+#pragma unroll
+  for (int u = 0; u < kElemsPerBlock / 1024; ++u) {
+    const int64_t e = (static_cast<int64_t>(base) + u * 256 + threadIdx.x) * 4;
+    if (e >= n) break;
+    if (vec && e + 3 < n) {
+      *reinterpret_cast<float4*>(dst + e) = src ? *reinterpret_cast<const float4*>(src + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      for (int k = 0; k < 4 && e + k < n; ++k) dst[e + k] = src ? src[e + k] : 0.f;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int agnn_gather_f32(int32_t n_items, const agnn_gather_item_t* items, agnn_stream_t stream_) {
+  using namespace agnn;
+  if (n_items < 0) return fail(AGNN_EINVAL, "gather: negative item count");
+  if (n_items > 0 && !items) return fail(AGNN_EINVAL, "gather: null item table");
+  for (int32_t i = 0; i < n_items; ++i) {
+    const agnn_gather_item_t& it = items[i];
+    if (it.n < 0 || it.n >= (int64_t{1} << 31)) return fail(AGNN_EINVAL, "gather: item %d has %lld floats", i, (long long)it.n);
+    if (it.n > 0 && !it.dst) return fail(AGNN_EINVAL, "gather: item %d: null destination", i);
+    if ((reinterpret_cast<uintptr_t>(it.dst) | reinterpret_cast<uintptr_t>(it.src)) & 3u) return fail(AGNN_EALIGN, "gather: item %d is not float-aligned", i);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  int32_t at = 0;
+  while (at < n_items) {
+    GatherTable t;
+    t.count = 0;
+    int64_t blocks = 0;
+    for (; at < n_items && t.count < AGNN_GATHER_MAX_ITEMS; ++at) {
+      const agnn_gather_item_t& it = items[at];
+      if (it.n == 0) continue;
+      const int64_t b = (it.n + kElemsPerBlock - 1) / kElemsPerBlock;
+      if (blocks + b >= (int64_t{1} << 31)) return fail(AGNN_EINVAL, "gather: too many floats in one call");
+      t.dst[t.count] = it.dst;
+      t.src[t.count] = it.src;
+      t.n[t.count] = static_cast<int32_t>(it.n);
+      t.first_block[t.count++] = static_cast<int32_t>(blocks);
+      blocks += b;
+    }
+    if (t.count == 0) continue;
+    t.first_block[t.count] = static_cast<int32_t>(blocks);
+    hipLaunchKernelGGL(k_gather, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, t);
+    if (int rc = check_launch("gather")) return rc;
+  }
+  return AGNN_OK;
+}
+
 namespace {
 __global__ void k_stamp(unsigned long long* slot) { *slot = wall_clock64(); }
 }  // namespace

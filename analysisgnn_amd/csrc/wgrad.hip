@@ -193,9 +193,13 @@ __global__ __launch_bounds__(256) void k_wgrad_batch(WgBatch b) {
 // dw[o][i] = sum_s slab[s][o][i] ;  db[o] = sum_s slab_b[s][o]   (fixed order: 8 interleaved partial sums, then a
 // fixed tree).  A block = 32 float2 columns x 8 slab groups, so the S slab reads of one output element are
 // spread over 8 threads with independent loads in flight instead of one thread walking S strided lines.
-__device__ __forceinline__ void wgrad_reduce_blocks(const float* __restrict__ slab, const float* __restrict__ slab_b, int S, int out_f, int in_f,
-                                                    int out_pad, int in_pad, float* __restrict__ dw, int64_t ld_dw, float* __restrict__ db,
-                                                    const int block, const int n_blocks) {
+// `store_w(o, i, t)` receives the finished column pair (i, i + 1) of output row o, `store_b(e, t)` the bias sum of row e (only
+// where `with_bias`): the one copy of the arithmetic serves the single destination below and the destination lists of the
+// gradient epilogue at the end of this file.
+template <typename StoreW, typename StoreB>
+__device__ __forceinline__ void wgrad_reduce_sums(const float* __restrict__ slab, const float* __restrict__ slab_b, int S, int out_f, int in_f,
+                                                  int out_pad, int in_pad, const bool with_bias, const int block, const int n_blocks,
+                                                  StoreW store_w, StoreB store_b) {
   __shared__ float2 part[8][32];
   const int col = threadIdx.x & 31, sg = threadIdx.x >> 5;
   const int half_in = in_f >> 1;
@@ -221,11 +225,11 @@ __device__ __forceinline__ void wgrad_reduce_blocks(const float* __restrict__ sl
       float2 t = part[0][col];
 #pragma unroll
       for (int g = 1; g < 8; ++g) { t.x += part[g][col].x; t.y += part[g][col].y; }
-      *reinterpret_cast<float2*>(dw + static_cast<int64_t>(o) * ld_dw + i) = t;
+      store_w(o, i, t);
     }
     __syncthreads();
   }
-  if (db != nullptr) {
+  if (with_bias) {
     // same 32 x 8 decomposition for the bias slabs (a serial walk over S slabs cost ~19 us of load latency)
     __shared__ float partb[8][32];
     for (int e0 = block * 32; e0 < out_f; e0 += n_blocks * 32) {
@@ -239,11 +243,19 @@ __device__ __forceinline__ void wgrad_reduce_blocks(const float* __restrict__ sl
         float t = partb[0][col];
 #pragma unroll
         for (int g = 1; g < 8; ++g) t += partb[g][col];
-        db[e] = t;
+        store_b(e, t);
       }
       __syncthreads();
     }
   }
+}
+
+__device__ __forceinline__ void wgrad_reduce_blocks(const float* __restrict__ slab, const float* __restrict__ slab_b, int S, int out_f, int in_f,
+                                                    int out_pad, int in_pad, float* __restrict__ dw, int64_t ld_dw, float* __restrict__ db,
+                                                    const int block, const int n_blocks) {
+  wgrad_reduce_sums(slab, slab_b, S, out_f, in_f, out_pad, in_pad, db != nullptr, block, n_blocks,
+                    [=](int o, int i, float2 t) { *reinterpret_cast<float2*>(dw + static_cast<int64_t>(o) * ld_dw + i) = t; },
+                    [=](int e, float t) { db[e] = t; });
 }
 
 __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ slab, const float* __restrict__ slab_b, int S,
@@ -440,4 +452,285 @@ extern "C" int agnn_wgrad_batch_f32(int32_t n_items, const agnn_wgrad_item_t* it
   if (int rc = check_launch("wgrad_batch")) return rc;
   hipLaunchKernelGGL(k_wgrad_reduce_batch, dim3(static_cast<unsigned>(red)), dim3(256), 0, s, rb);
   return check_launch("wgrad_batch(reduce)");
+}
+
+// ---- gradient epilogue: slab sums and LayerNorm column sums stored straight into their final destinations ---------------------
+// The products above only feed the optimizer, and so do the dgamma / dbeta column sums that are pending at the same flush points.
+// Their results used to be written to temporaries and copied on: a fan-out launch for the SAGE layers' per-relation parameters
+// (the summed root weight and bias replicated R times), a gather of every gradient into the flat buffer, a launch of their own
+// for the column sums.  Here ONE reduction launch per flush serves the products and the column sums, and each result element is
+// stored to every destination that wants it.  The arithmetic is that of wgrad_reduce_blocks / na_colsum_block (normact.hip), term
+// for term; only the stores differ.
+namespace {
+
+constexpr int kEpiRecMax = 64;        // weight destinations per reduction launch; a call that names more (16 SAGE products of 4 relations
+                                      // have 128) gets a further reduction launch per 64: same sums, one more launch
+constexpr int kEpiDbMax = 48;         // bias destinations per reduction launch
+constexpr int kEpiSumMax = AGNN_GRAD_MAX_SUMS;   // column sums per call (agnn_norm_act_colsum_batch_f32's limit as well)
+constexpr int kEpiPartRows = 1024;    // partial rows agnn_norm_act_bwd_f32 leaves at most (normact.hip: kBwdBlocks)
+
+struct EpiRec {
+  float* p;
+  int32_t ld, c0, c1, scalar;
+};
+struct EpiItem {
+  const float* slab;
+  const float* slab_b;
+  int32_t S, out_f, in_f, out_pad, in_pad;
+  int16_t rec0, rec1, db0, db1;
+};
+struct EpiSum {
+  const float* part;
+  float* dgamma;
+  float* dbeta;
+  int32_t n_rows, H;
+};
+struct EpiBatch {                     // a kernel argument: must stay below 4 KB
+  EpiItem it[kWgBatchMax];
+  EpiRec rec[kEpiRecMax];
+  float* db[kEpiDbMax];
+  EpiSum sum[kEpiSumMax];
+  int32_t first[kWgBatchMax + kEpiSumMax + 1];
+  int32_t n_items, n_all;
+};
+static_assert(sizeof(EpiBatch) <= 4096, "EpiBatch travels as a kernel argument");
+
+// wgrad_reduce_sums with a destination list: every finished element goes to each record whose column range holds it
+__device__ __forceinline__ void epi_product(const EpiBatch& b, const EpiItem& r, const int block, const int n_blocks) {
+  const int rec0 = r.rec0, rec1 = r.rec1, db0 = r.db0, db1 = r.db1;
+  wgrad_reduce_sums(
+      r.slab, r.slab_b, r.S, r.out_f, r.in_f, r.out_pad, r.in_pad, db1 > db0, block, n_blocks,
+      [&](int o, int i, float2 t) {
+        for (int q = rec0; q < rec1; ++q) {                 // block-uniform trip count, records read through scalar loads
+          const EpiRec d = b.rec[q];
+          float* row = d.p + static_cast<int64_t>(o) * d.ld - d.c0;
+          if (d.scalar) {                                   // odd column count: float by float, the range checked per column
+            if (i >= d.c0 && i < d.c1) row[i] = t.x;
+            if (i + 1 >= d.c0 && i + 1 < d.c1) row[i + 1] = t.y;
+          } else if (i >= d.c0 && i < d.c1) {               // c0, c1 even: a column pair lies inside or outside as a whole
+            *reinterpret_cast<float2*>(row + i) = t;
+          }
+        }
+      },
+      [&](int e, float t) {
+        for (int q = db0; q < db1; ++q) b.db[q][e] = t;
+      });
+}
+
+// na_colsum_block (normact.hip) on a 256-thread block: that kernel runs 32 chains of additions per column, chain `grp` adding
+// part[grp + 32 k], k = 0 .. 31, in that order per pass of 1024 rows, and then sums the chains in index order.  Here a thread
+// carries the four chains g8, g8 + 8, g8 + 16, g8 + 24 in four accumulators; every chain adds the same terms in the same order.
+// (Not one function with na_colsum_block: the chains are laid out over the block differently.  The loads of the four chains are
+// independent; in the c2s step both launches that carry column sums are shorter than the pairs they replace, 29.0 against 35.6
+// and 11.5 against 16.0 us (profiles/grad_delivery.md).  tests/test_gpu_grad_delivery.py holds the bits together.)
+__device__ __forceinline__ void epi_colsum(const EpiSum& c, const int block) {
+  __shared__ float sm[32][33];
+  const int col = threadIdx.x & 31, g8 = threadIdx.x >> 5;
+  const int width = 2 * c.H, n_rows = c.n_rows;
+  const int j = block * 32 + col;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  if (j < width) {
+    for (int w00 = 0; w00 < n_rows; w00 += 32 * 32) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int w0 = w00 + g8 + 8 * q;
+        if (w0 >= n_rows) continue;                       // (that chain makes no such pass in na_colsum_block either)
+        float v[32];
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+          const int w = w0 + 32 * k;
+          v[k] = w < n_rows ? c.part[static_cast<int64_t>(w) * width + j] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 32; ++k) s[q] += v[k];
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) sm[g8 + 8 * q][col] = s[q];
+  __syncthreads();
+  if (g8 == 0 && j < width) {
+    float t = sm[0][col];
+#pragma unroll
+    for (int k = 1; k < 32; ++k) t += sm[k][col];
+    if (j < c.H) c.dgamma[j] = t; else c.dbeta[j - c.H] = t;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_grad_epilogue(EpiBatch b) {
+  int i = 0;
+  const int blk = blockIdx.x;
+  while (i + 1 < b.n_all && blk >= b.first[i + 1]) ++i;             // block-uniform: item type and trip counts are too
+  const int local = blk - b.first[i];
+  if (i < b.n_items) epi_product(b, b.it[i], local, b.first[i + 1] - b.first[i]);
+  else epi_colsum(b.sum[i - b.n_items], local);
+}
+
+// one destination as the host sees it: `rows` segments of `cols` floats, `ld` apart
+struct EpiSpan {
+  const float* p;
+  int64_t ld;
+  int32_t rows, cols;
+  int32_t item, c0, c1;             // item < 0: not a weight record (never a declared copy)
+};
+
+bool spans_overlap(const EpiSpan& a, const EpiSpan& b) {
+  const float* a_end = a.p + static_cast<int64_t>(a.rows - 1) * a.ld + a.cols;
+  const float* b_end = b.p + static_cast<int64_t>(b.rows - 1) * b.ld + b.cols;
+  if (a_end <= b.p || b_end <= a.p) return false;
+  if (a.rows > 1 && b.rows > 1 && a.ld == b.ld) {           // column blocks of one matrix: compare the column windows
+    int64_t r = (b.p - a.p) % a.ld;
+    if (r < 0) r += a.ld;
+    if (r >= a.cols && r + b.cols <= a.ld) return false;
+  }
+  return true;                                              // (different strides with interleaved hulls: refused, not analysed)
+}
+
+}  // namespace
+
+static void epi_as_wgrad(int32_t n_items, const agnn_grad_item_t* items, agnn_wgrad_item_t* out) {
+  for (int i = 0; i < n_items; ++i) {
+    const agnn_grad_item_t& g = items[i];
+    out[i] = agnn_wgrad_item_t{g.dy, g.x, nullptr, nullptr, g.ld_dy, g.ld_x, g.in_f, g.n, g.out_f, g.in_f};
+  }
+}
+
+extern "C" size_t agnn_grad_epilogue_workspace_bytes(int32_t n_items, const agnn_grad_item_t* items) {
+  if (n_items <= 0 || n_items > kWgBatchMax || !items) return 0;
+  agnn_wgrad_item_t w[kWgBatchMax];
+  epi_as_wgrad(n_items, items, w);
+  return agnn_wgrad_batch_workspace_bytes(n_items, w);
+}
+
+extern "C" int agnn_grad_epilogue_f32(int32_t n_items, const agnn_grad_item_t* items, int32_t n_sums, const agnn_colsum_item_t* sums,
+                                      void* workspace, size_t workspace_bytes, agnn_stream_t stream_) {
+  using namespace agnn;
+  if (n_items < 0 || n_items > kWgBatchMax || (n_items > 0 && !items)) return fail(AGNN_EINVAL, "grad_epilogue: %d products (0 .. %d)", n_items, kWgBatchMax);
+  if (n_sums < 0 || n_sums > kEpiSumMax || (n_sums > 0 && !sums)) return fail(AGNN_EINVAL, "grad_epilogue: %d column sums (0 .. %d)", n_sums, kEpiSumMax);
+  if (n_items == 0 && n_sums == 0) return AGNN_OK;
+  BatchPlan bp;
+  bp.n = 0;
+  bp.total_floats = 0;
+  float* ws = nullptr;
+  if (n_items > 0) {
+    agnn_wgrad_item_t w[kWgBatchMax];
+    epi_as_wgrad(n_items, items, w);
+    if (int rc = batch_plan(n_items, w, bp)) return rc;
+    if (!workspace || workspace_bytes < bp.total_floats * sizeof(float) + 256) return fail(AGNN_ENOMEM, "grad_epilogue: workspace too small");
+    ws = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t{255});
+  }
+  // ---- validation: operands as agnn_wgrad_batch_f32, then every destination, then overlaps
+  static thread_local EpiSpan spans[kWgBatchMax * 2 * AGNN_PACK_MAX_SRC + 2 * kEpiSumMax];
+  int n_spans = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const agnn_grad_item_t& it = items[i];
+    if ((it.out_f & 1) || (it.in_f & 1) || (it.ld_dy & 1) || (it.ld_x & 1)) return fail(AGNN_EALIGN, "grad_epilogue: item %d: widths and leading dimensions must be even", i);
+    if (!it.dy || !it.x) return fail(AGNN_EINVAL, "grad_epilogue: item %d: null argument", i);
+    if ((reinterpret_cast<uintptr_t>(it.dy) | reinterpret_cast<uintptr_t>(it.x)) & 7u) return fail(AGNN_EALIGN, "grad_epilogue: item %d: pointers must be 8-byte aligned", i);
+    if (it.ld_dy < it.out_f || it.ld_x < it.in_f) return fail(AGNN_EINVAL, "grad_epilogue: item %d: leading dimension smaller than the width", i);
+    if ((static_cast<int64_t>(bp.rps[i]) + 128) * (it.ld_dy > it.ld_x ? it.ld_dy : it.ld_x) * 4 >= (int64_t{1} << 32))
+      return fail(AGNN_EINVAL, "grad_epilogue: item %d: a row slice (%d rows x ld) exceeds the kernel's 32-bit byte offsets", i, bp.rps[i]);
+    if (it.n_dw < 0 || it.n_dw > AGNN_PACK_MAX_SRC || it.n_db < 0 || it.n_db > AGNN_PACK_MAX_SRC || it.n_dw + it.n_db == 0)
+      return fail(AGNN_EINVAL, "grad_epilogue: item %d: %d weight and %d bias destinations (0 .. %d each, one at least)", i, it.n_dw, it.n_db, AGNN_PACK_MAX_SRC);
+    for (int k = 0; k < it.n_dw; ++k) {
+      const agnn_grad_dst_t& d = it.dw[k];
+      const int cols = d.c1 - d.c0;
+      if (!d.p || d.c0 < 0 || cols <= 0 || d.c1 > it.in_f || d.ld < cols || d.ld >= (int64_t{1} << 31))
+        return fail(AGNN_EINVAL, "grad_epilogue: item %d: destination %d: columns [%d, %d) of %d, ld %lld", i, k, d.c0, d.c1, it.in_f, (long long)d.ld);
+      if (reinterpret_cast<uintptr_t>(d.p) & 3u) return fail(AGNN_EALIGN, "grad_epilogue: item %d: destination %d is not a float pointer", i, k);
+      if (!(cols & 1) && ((d.c0 & 1) || (d.ld & 1) || (reinterpret_cast<uintptr_t>(d.p) & 7u)))
+        return fail(AGNN_EALIGN, "grad_epilogue: item %d: destination %d: an even column block needs an even c0, an even ld and an 8-byte aligned pointer", i, k);
+      spans[n_spans++] = EpiSpan{d.p, d.ld, it.out_f, cols, i, d.c0, d.c1};
+    }
+    for (int k = 0; k < it.n_db; ++k) {
+      if (!it.db[k]) return fail(AGNN_EINVAL, "grad_epilogue: item %d: null bias destination %d", i, k);
+      if (reinterpret_cast<uintptr_t>(it.db[k]) & 3u) return fail(AGNN_EALIGN, "grad_epilogue: item %d: bias destination %d is not a float pointer", i, k);
+      spans[n_spans++] = EpiSpan{it.db[k], it.out_f, 1, it.out_f, -1, 0, 0};
+    }
+  }
+  for (int i = 0; i < n_sums; ++i) {
+    const agnn_colsum_item_t& it = sums[i];
+    if (it.n <= 0 || it.H <= 0 || (it.H & 3) || it.H > 2048 || !it.workspace || !it.dgamma || !it.dbeta)
+      return fail(AGNN_EINVAL, "grad_epilogue: column sum %d: bad sizes or null argument", i);
+    if (it.workspace_bytes < static_cast<size_t>(kEpiPartRows) * 2 * it.H * sizeof(float)) return fail(AGNN_ENOMEM, "grad_epilogue: column sum %d: workspace too small", i);
+    if ((reinterpret_cast<uintptr_t>(it.dgamma) | reinterpret_cast<uintptr_t>(it.dbeta) | reinterpret_cast<uintptr_t>(it.workspace)) & 3u)
+      return fail(AGNN_EALIGN, "grad_epilogue: column sum %d: misaligned", i);
+    spans[n_spans++] = EpiSpan{it.dgamma, it.H, 1, it.H, -1, 0, 0};
+    spans[n_spans++] = EpiSpan{it.dbeta, it.H, 1, it.H, -1, 0, 0};
+  }
+  for (int a = 0; a < n_spans; ++a)
+    for (int c = a + 1; c < n_spans; ++c) {
+      const EpiSpan &sa = spans[a], &sc = spans[c];
+      // two records of one product that name the same range AND the same place receive the same value at every address
+      if (sa.item >= 0 && sa.item == sc.item && sa.c0 == sc.c0 && sa.c1 == sc.c1 && sa.p == sc.p && sa.ld == sc.ld) continue;
+      if (spans_overlap(sa, sc)) return fail(AGNN_EINVAL, "grad_epilogue: destinations %d and %d of the call overlap", a, c);
+    }
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  // ---- the products: agnn_wgrad_batch_f32's launch, unchanged
+  if (n_items > 0) {
+    WgBatch wb{};
+    wb.n = n_items;
+    int wg = 0;
+    for (int i = 0; i < n_items; ++i) {
+      const agnn_grad_item_t& it = items[i];
+      const int out_pad = bp.tiles_out[i] * 128, in_pad = bp.tiles_in[i] * 128;
+      wb.it[i] = WgArgs{it.dy, it.x, it.ld_dy, it.ld_x, static_cast<int32_t>(it.n), it.out_f, it.in_f, bp.rps[i], bp.tiles_in[i], ws + bp.slab_off[i],
+                        it.n_db > 0 ? ws + bp.slabb_off[i] : nullptr, out_pad, in_pad};
+      wb.tiles[i] = bp.tiles_out[i] * bp.tiles_in[i];
+      wb.first[i] = wg;
+      wg += wb.tiles[i] * bp.S[i];
+    }
+    wb.first[n_items] = wg;
+    hipLaunchKernelGGL(k_wgrad_batch, dim3(static_cast<unsigned>(wg)), dim3(256), 0, s, wb);
+    if (int rc = check_launch("grad_epilogue(products)")) return rc;
+  }
+  // ---- the reduction: as many products per launch as the record tables hold, the column sums with the last
+  int at = 0;
+  do {
+    EpiBatch eb{};
+    int n = 0, n_rec = 0, n_db = 0, blocks = 0;
+    while (at < n_items && n_rec + items[at].n_dw <= kEpiRecMax && n_db + items[at].n_db <= kEpiDbMax) {
+      const agnn_grad_item_t& it = items[at];
+      EpiItem& e = eb.it[n];
+      e.slab = ws + bp.slab_off[at];
+      e.slab_b = it.n_db > 0 ? ws + bp.slabb_off[at] : nullptr;
+      e.S = bp.S[at];
+      e.out_f = it.out_f;
+      e.in_f = it.in_f;
+      e.out_pad = bp.tiles_out[at] * 128;
+      e.in_pad = bp.tiles_in[at] * 128;
+      e.rec0 = static_cast<int16_t>(n_rec);
+      for (int k = 0; k < it.n_dw; ++k) {
+        const agnn_grad_dst_t& d = it.dw[k];
+        eb.rec[n_rec++] = EpiRec{d.p, static_cast<int32_t>(d.ld), d.c0, d.c1, (d.c1 - d.c0) & 1};
+      }
+      e.rec1 = static_cast<int16_t>(n_rec);
+      e.db0 = static_cast<int16_t>(n_db);
+      for (int k = 0; k < it.n_db; ++k) eb.db[n_db++] = it.db[k];
+      e.db1 = static_cast<int16_t>(n_db);
+      eb.first[n] = blocks;
+      int64_t rb = (static_cast<int64_t>(it.out_f) * (it.in_f >> 1) + 31) / 32;       // agnn_wgrad_batch_f32's block count
+      if (rb > 1024) rb = 1024;
+      blocks += static_cast<int>(rb);
+      ++n;
+      ++at;
+    }
+    eb.n_items = n;
+    if (at == n_items)
+      for (int i = 0; i < n_sums; ++i) {
+        const agnn_colsum_item_t& it = sums[i];
+        int nb = static_cast<int>((it.n + 3) / 4);
+        if (nb > kEpiPartRows) nb = kEpiPartRows;
+        eb.sum[i] = EpiSum{static_cast<const float*>(it.workspace), it.dgamma, it.dbeta, nb, it.H};
+        eb.first[n++] = blocks;
+        blocks += (2 * it.H + 31) / 32;
+      }
+    eb.first[n] = blocks;
+    eb.n_all = n;
+    if (blocks > 0) {
+      hipLaunchKernelGGL(k_grad_epilogue, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, eb);
+      if (int rc = check_launch("grad_epilogue(reduce)")) return rc;
+    }
+  } while (at < n_items);
+  return AGNN_OK;
 }

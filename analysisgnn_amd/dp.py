@@ -86,6 +86,11 @@ def plan_parameters(model: torch.nn.Module, late: Iterable[torch.nn.Parameter] =
     return params, tight
 
 
+def _grad_in_place() -> bool:
+    from . import linear
+    return bool(linear.GRAD_IN_PLACE)
+
+
 class FlatGradBuffer:
     """All gradients of `params` in one contiguous fp32 buffer (the all-reduce message).
 
@@ -93,8 +98,10 @@ class FlatGradBuffer:
       * `views=True`  — `.grad` of each parameter is a view into the buffer, backward accumulates straight into
         the message (no pack step; costs one tiny accumulate launch per parameter, fine when GPU-bound);
       * `views=False` — autograd hands over fresh gradient tensors (no per-parameter accumulate launches, which
-        dominate when a step is launch-bound: ~130 parameters here) and `pack()` gathers them with ONE cat;
-        `.grad` then become views of the buffer so the optimizer sees the reduced / clipped values.
+        dominate when a step is launch-bound: ~130 parameters here) and `pack()` gathers them;
+        `.grad` then become views of the buffer so the optimizer sees the reduced / clipped values.  On a GPU the
+        parameters' slots are registered (linear.register_grad_slots): the native kernels that produce a gradient write
+        it into its slot themselves (linear.GRAD_IN_PLACE), and `pack()` only copies or zero-fills the rest.
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter], views: bool = True, tight: Optional[set] = None,
@@ -129,6 +136,16 @@ class FlatGradBuffer:
         self.cut = self.offsets[self.n_early]                # flat[:cut] = early bucket, flat[cut:] = late bucket
         if views:
             self._assign_views()
+        elif dev.type == "cuda":
+            import weakref
+            from . import linear
+            linear.register_grad_slots(self, self.params, self.flat, self.offsets)
+            weakref.finalize(self, linear.unregister_grad_slots, id(self))       # removing the buffer removes its entries
+
+    def close(self) -> None:
+        """Withdraw the parameters' slots from the registry (also done when the buffer is collected)."""
+        from . import linear
+        linear.unregister_grad_slots(id(self))
 
     def _assign_views(self) -> None:
         for p, k, o in zip(self.params, self.sizes, self.offsets):
@@ -141,6 +158,9 @@ class FlatGradBuffer:
             for p in self.params:
                 p.grad = None
             self._packed = set()
+            if self.flat.is_cuda:
+                from .linear import reset_grad_slots
+                reset_grad_slots(self.params)
 
     def pack(self, part: Optional[str] = None) -> None:
         """views=False: gather the fresh gradients into the flat buffer (one launch; `part` = "early" / "late": one bucket, one
@@ -156,18 +176,61 @@ class FlatGradBuffer:
             if (part is not None and part != name) or name in done or lo == hi:
                 done.add(name) if lo == hi else None
                 continue
-            parts = []
-            for i in range(lo, hi):
-                p, k, o, o_next = self.params[i], self.sizes[i], self.offsets[i], self.offsets[i + 1]
-                parts.append(p.grad.reshape(-1) if p.grad is not None else self._none[:k])
-                if o_next - o > k:
-                    parts.append(self._pad[: o_next - o - k])
-            torch.cat(parts, out=self.flat[self.offsets[lo]:self.offsets[hi]])
+            if self.flat.is_cuda and _grad_in_place():
+                self._pack_native(lo, hi)
+            else:                                    # CPU buffers, and linear.GRAD_IN_PLACE off: the one-cat gather as it was
+                parts = []
+                for i in range(lo, hi):
+                    p, k, o, o_next = self.params[i], self.sizes[i], self.offsets[i], self.offsets[i + 1]
+                    parts.append(p.grad.reshape(-1) if p.grad is not None else self._none[:k])
+                    if o_next - o > k:
+                        parts.append(self._pad[: o_next - o - k])
+                torch.cat(parts, out=self.flat[self.offsets[lo]:self.offsets[hi]])
             for i in range(lo, hi):
                 p, k, o = self.params[i], self.sizes[i], self.offsets[i]
                 p.grad = self.flat[o:o + k].view_as(p)
             done.add(name)
         self._packed = done
+
+    def _pack_native(self, lo: int, hi: int) -> None:
+        """The gradients of parameters lo .. hi - 1 that are not in their slots yet — made by torch ops or by kernels that do not
+        take a destination — copied there, and the slots of parameters that took no gradient zero-filled (they hold the last
+        step's values), by one `agnn_pack_f32` launch (up to 24 pieces) or `agnn_gather_f32` (128 pieces per launch).  The few floats of padding behind a slot whose size is no
+        multiple of four are zero-filled as well: after `pack()` every element of the buffer has been written this step."""
+        from . import _lib
+        from .linear import reset_grad_slots
+        from .params import pack
+        items = []
+        for i in range(lo, hi):
+            p, k, o, o_next = self.params[i], self.sizes[i], self.offsets[i], self.offsets[i + 1]
+            g = p.grad
+            if o_next - o > k:
+                items.append((self.flat[o + k:o_next].view(1, -1), []))
+            if k == 0:
+                continue
+            slot = self.flat[o:o + k]
+            if g is None:
+                items.append((slot.view(1, -1), []))
+                continue
+            if g.data_ptr() == slot.data_ptr() and g.shape == p.shape and g.is_contiguous():
+                continue                                       # written in place by its producer
+            if g.dtype != torch.float32 or g.device != self.flat.device:
+                raise ValueError("FlatGradBuffer.pack: fp32 gradients on the buffer's device expected")
+            items.append((slot.view(1, -1), [g.contiguous().view(1, -1)]))
+        if len(items) <= _lib.PACK_MAX_ITEMS:
+            if items:
+                pack(items, self.flat.device)
+        else:
+            # more pieces than one agnn_pack_f32 launch takes (HGT's relation parameters, a GRU on the library path): the plain
+            # gather, 128 pieces per launch — a launch per 24 cost more than the two torch.cat launches it replaced
+            arr = (_lib.GatherItem * len(items))()
+            keep = []
+            for a, (dst, srcs) in zip(arr, items):
+                a.dst, a.n = dst.data_ptr(), dst.numel()
+                a.src = srcs[0].data_ptr() if srcs else None
+                keep.extend(srcs)
+            _lib.check(_lib.load().agnn_gather_f32(len(items), arr, _lib.stream_ptr(self.flat.device)), "agnn_gather_f32")
+        reset_grad_slots(self.params[lo:hi])
 
     def all_reduce_mean(self, world: Optional[int] = None) -> None:
         """SUM over ranks then divide: the same mean DDP applies."""

@@ -12,7 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, resident
-from .linear import ColsumItem, all_steal, defer, deferring, leaf_refs
+from .linear import ColsumItem, all_steal, defer, deferring, grad_slot_groups, leaf_refs, slot_group
 
 PRE_RELU, POST_RELU = 1, 2
 ENABLED = True
@@ -36,14 +36,15 @@ def _al16(t: torch.Tensor) -> torch.Tensor:
 
 class _NormAct(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, p, flags, call_id, seg=0, defer_ok=False, steal_refs=None, pre=None):
+    def forward(ctx, x, gamma, beta, eps, p, flags, call_id, seg=0, defer_ok=False, steal_refs=None, pre=None, slot_groups=None):
         """x [n, H]; gamma / beta [H]; statistics over segments of `seg` floats (0 = the whole row).  `defer_ok`: gamma / beta
         are leaves, or reach their leaves through views only (their gradients may be produced late: linear.defer_weight_grads).
         `pre` = [y, mean, rstd] already computed by a fused producer (heads.fused_head_logits): nothing is launched here, the
-        node only carries the backward pass."""
+        node only carries the backward pass.  `slot_groups`: (linear.slot_group of gamma, of beta) where the caller reshaped them."""
         dev = _lib.require_gpu(x, gamma, beta)
         ctx.defer_ok = bool(defer_ok) or (gamma.is_leaf and beta.is_leaf)
         ctx.steal_refs = leaf_refs(gamma, beta) if steal_refs is None else tuple(steal_refs)   # reshaped operands: the caller names the leaves
+        ctx.slot_groups = (slot_group(gamma), slot_group(beta)) if slot_groups is None else tuple(slot_groups)
         lib = _lib.load()
         x = x if (x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0) else x.contiguous()
         n, H = x.shape
@@ -75,14 +76,22 @@ class _NormAct(torch.autograd.Function):
         dy = dy if (dy.stride(1) == 1 and dy.stride(0) % 4 == 0 and dy.data_ptr() % 16 == 0) else dy.contiguous()
         n, H = x.shape
         dx = torch.empty_like(x)
-        dgamma = torch.empty_like(gamma)
-        dbeta = torch.empty_like(beta)
         nws = int(lib.agnn_norm_act_workspace_bytes(H))
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
         rng = used[0] if p > 0 else None                     # the forward call's own (seed, step), not the live counter
         # dgamma / dbeta only feed the optimizer: with deferred weight gradients (linear.defer_weight_grads) their column-sum
         # launch leaves the chain too (the closure works on aliases: see linear._LinearFn.backward)
         later = ctx.defer_ok and deferring(dy) and all_steal(ctx.steal_refs)
+        # ... and then writes the two parameters' slots of the flat gradient buffer, where there is one (linear.grad_slots)
+        own = None
+        if later and ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and ctx.slot_groups[0] and ctx.slot_groups[1]:
+            own = grad_slot_groups(ctx.slot_groups, (gamma.shape, beta.shape))
+        if own is not None:
+            dgamma, dbeta = own
+            del own
+        else:
+            dgamma = torch.empty_like(gamma)
+            dbeta = torch.empty_like(beta)
         _lib.check(lib.agnn_norm_act_bwd_f32(x.data_ptr(), x.stride(0), gamma.data_ptr(), beta.data_ptr(), seg, n, H, eps, p, flags,
                                              _lib.ptr(rng), call_id, dy.data_ptr(), dy.stride(0), mean.data_ptr(), rstd.data_ptr(),
                                              dx.data_ptr(), dx.stride(0), None if later else dgamma.data_ptr(),
@@ -91,7 +100,7 @@ class _NormAct(torch.autograd.Function):
         if later:
             dg_k, db_k = dgamma.detach(), dbeta.detach()
             defer(ColsumItem(ws, n, H, dg_k, db_k), dev)       # pending column sums of a flush go out in one launch
-        return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None
 
 
 def _ok16(t: torch.Tensor) -> bool:
@@ -202,7 +211,7 @@ def grouped_norm_act(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, e
         return F.layer_norm(y, (H,), None, None, eps) * gamma + beta
     view_only = all(t.is_leaf or getattr(t, "_agnn_wgrad_deferrable", False) for t in (gamma, beta))
     y = _NormAct.apply(x.reshape(N, W), gamma.reshape(W), beta.reshape(W), eps, 0.0, PRE_RELU if pre_relu else 0,
-                       next(_CALL_IDS) & 0xFFFFFFFF, H, view_only, leaf_refs(gamma, beta), pre)
+                       next(_CALL_IDS) & 0xFFFFFFFF, H, view_only, leaf_refs(gamma, beta), pre, (slot_group(gamma), slot_group(beta)))
     return y.view(N, G, H)
 
 

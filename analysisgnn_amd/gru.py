@@ -11,8 +11,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, resident
-from .linear import (WgItem, all_steal, defer, defer_home, deferring, leaf_refs, mark_wgrad_async, weight_grad, weight_grad_batch,
-                     wgrad_stream)
+from .linear import (WgItem, all_steal, defer, defer_home, deferring, grad_slot_groups, leaf_refs, mark_wgrad_async, slot_group, weight_grad,
+                     weight_grad_batch, wgrad_stream)
 
 KERNEL_HIDDEN = (64, 128)      # hidden sizes per direction the kernels are instantiated for (H = 128 / 256 hybrid models)
 
@@ -76,6 +76,7 @@ class _GRULayer(torch.autograd.Function):
         ctx.dims = (B, T, I, Hh)
         ctx.wg_async = all(getattr(t, "_agnn_wgrad_async", False) or t.is_leaf for t in (w_ih, w_hh, b_ih, b_hh))
         ctx.steal_refs = leaf_refs(w_ih, w_hh, b_ih, b_hh)
+        ctx.slot_groups = tuple(slot_group(t) for t in (w_ih, w_hh, b_ih, b_hh))     # where the stacked gradients finally belong
         return out
 
     @staticmethod
@@ -97,10 +98,22 @@ class _GRULayer(torch.autograd.Function):
         # Everything that only feeds the optimizer leaves the recurrence chain (layer l-1's kernel waits for dx alone).
         # Forked AFTER dx is queued: the weight-gradient GEMMs then run beside the next layer's recurrence kernel
         # (64 of 256 CUs) instead of halving the speed of the dx GEMM the chain is waiting for.
-        dw_ih = torch.empty((6 * Hh, I), dtype=torch.float32, device=dev)
-        db_ih = torch.empty((6 * Hh,), dtype=torch.float32, device=dev)
-        dw_hh = torch.empty((2, 3 * Hh, Hh), dtype=torch.float32, device=dev)            # both directions land in the stacked
-        db_hh = torch.empty((2, 3 * Hh), dtype=torch.float32, device=dev)                # gradients directly (no torch.stack)
+        # off the chain only while every parameter behind the stacked operands takes its gradient over without a kernel
+        # (no .grad yet, no hook): otherwise AccumulateGrad adds on this stream at once and must find the values there
+        off_chain = ctx.wg_async and all_steal(ctx.steal_refs)
+        own = None
+        if off_chain and I % 2 == 0 and all(ctx.needs_input_grad[1:5]):
+            # the direction pairs' slots of the flat gradient buffer lie back to back: the products write them as the stacks
+            own = grad_slot_groups(ctx.slot_groups, ((6 * Hh, I), (2, 3 * Hh, Hh), (6 * Hh,), (2, 3 * Hh)),
+                                   lambda v: all(t is not None and t.data_ptr() % 8 == 0 for t in v))
+        if own is not None:
+            dw_ih, dw_hh, db_ih, db_hh = own
+            del own
+        else:
+            dw_ih = torch.empty((6 * Hh, I), dtype=torch.float32, device=dev)
+            db_ih = torch.empty((6 * Hh,), dtype=torch.float32, device=dev)
+            dw_hh = torch.empty((2, 3 * Hh, Hh), dtype=torch.float32, device=dev)            # both directions land in the stacked
+            db_hh = torch.empty((2, 3 * Hh), dtype=torch.float32, device=dev)                # gradients directly (no torch.stack)
 
         def weight_grads():
             items = []
@@ -114,10 +127,6 @@ class _GRULayer(torch.autograd.Function):
             for d in range(2):
                 items.append(WgItem(dgh2[:, d * 3 * Hh:(d + 1) * 3 * Hh], hp2[:, d * Hh:(d + 1) * Hh], True, dw_hh[d], db_hh[d]))
             weight_grad_batch(items)            # the layer's three products in one launch pair
-
-        # off the chain only while every parameter behind the stacked operands takes its gradient over without a kernel
-        # (no .grad yet, no hook): otherwise AccumulateGrad adds on this stream at once and must find the values there
-        off_chain = ctx.wg_async and all_steal(ctx.steal_refs)
 
         def forked():
             with wgrad_stream(dev, dgi, dgh, y, x2, hp, dw_ih, db_ih, dw_hh, db_hh, active=off_chain, kind="sequence"):

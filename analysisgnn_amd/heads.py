@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from . import _lib, resident
 from .fused import grouped_norm_act
-from .linear import all_steal, defer, deferring, leaf_refs, linear, mark_wgrad_async, wgrad_stream
+from .linear import all_steal, defer, deferring, grad_slot_groups, leaf_refs, linear, mark_wgrad_async, slot_group, wgrad_stream
 from .params import cat_rows, stack_rows
 
 
@@ -121,6 +121,7 @@ class _GroupedProj(torch.autograd.Function):
         ctx._wg_async_in = all(t is None or t.is_leaf or getattr(t, "_agnn_wgrad_async", False) for t in (w, b))
         ctx._wg_defer_in = all(t is None or t.is_leaf or getattr(t, "_agnn_wgrad_deferrable", False) for t in (w, b))
         ctx.steal_refs = leaf_refs(w, b)
+        ctx.slot_groups = (slot_group(w), slot_group(b))         # where dw / db finally belong (linear.grad_slot_groups)
         a = _lib.f32c(a)
         w = _lib.f32c(w)
         if w.data_ptr() % 16:
@@ -154,8 +155,17 @@ class _GroupedProj(torch.autograd.Function):
         need_w = ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2])
         dw = db = None
         if need_w:                                   # optimizer-only outputs: deferred, or on the weight-gradient stream (linear.py)
-            dw = torch.empty_like(w)
-            db = torch.empty((sum_c,), dtype=torch.float32, device=dev) if has_b else None
+            off_chain = ctx.wg_async and all_steal(ctx.steal_refs)      # else: AccumulateGrad adds on THIS stream, right now
+            own = None
+            if off_chain and ctx.needs_input_grad[1] and ctx.needs_input_grad[2] == has_b and ctx.slot_groups[0]:
+                # k_gproj_dw's slab sum writes the parameters' slots of the flat gradient buffer themselves
+                own = grad_slot_groups(ctx.slot_groups, (w.shape, (sum_c,)), lambda v: v[0].data_ptr() % 8 == 0)
+            if own is not None:
+                dw, db = own
+                del own
+            else:
+                dw = torch.empty_like(w)
+                db = torch.empty((sum_c,), dtype=torch.float32, device=dev) if has_b else None
             dw_k, db_k = dw.detach(), (db.detach() if db is not None else None)     # aliases: see linear._LinearFn.backward
 
             def weight_grads():
@@ -164,7 +174,6 @@ class _GroupedProj(torch.autograd.Function):
                 _lib.check(lib.agnn_gproj_bwd_f32(dout.data_ptr(), dout.stride(0), a.data_ptr(), a.stride(0), w.data_ptr(),
                                                   offs_t.data_ptr(), G, K, tiles, sum_c, N, None, 0, dw_k.data_ptr(), _lib.ptr(db_k),
                                                   ws.data_ptr(), nws, _lib.stream_ptr(dev)), "agnn_gproj_bwd_f32")
-            off_chain = ctx.wg_async and all_steal(ctx.steal_refs)      # else: AccumulateGrad adds on THIS stream, right now
             if off_chain and ctx.wg_defer and deferring(dout):
                 defer(weight_grads, dev)
             else:

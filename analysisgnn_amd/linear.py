@@ -222,10 +222,13 @@ def _run_deferred(fns) -> None:
                 if t is not None:
                     t.record_stream(here)
     with torch.no_grad():                # a flush may run outside a backward pass (FlatGradBuffer.pack): gradient math, never recorded
-        if items:
-            weight_grad_batch(items)
-        if sums:
-            colsum_batch(sums)
+        if GRAD_IN_PLACE and BATCH and (items or sums):
+            grad_epilogue(items, sums)   # one reduction launch per group of products, the column sums with the last of them
+        else:
+            if items:
+                weight_grad_batch(items)
+            if sums:
+                colsum_batch(sums)
         for fn in fns:
             if not isinstance(fn, (WgItem, ColsumItem)):
                 fn()
@@ -317,6 +320,114 @@ def join_wgrad() -> None:
     _WG.get("join", {}).clear()
 
 
+# ------------------------------------------------------------------------------------------------------------
+# Gradients delivered in place.  With dp.FlatGradBuffer(views=False) every parameter has a slot in the flat gradient buffer
+# that `pack()` would copy its gradient into.  A producer that allocates a gradient for a native kernel to fill asks here
+# first and lets the kernel write the slot itself: AccumulateGrad takes the slot view over as it takes a fresh tensor, and
+# `pack()` finds the gradient already in place.  Only where `all_steal` holds (`.grad` is None: with accumulation the slot
+# holds the sum autograd is about to add onto), once per parameter and backward pass (a parameter used twice gets a fresh
+# tensor the second time), and only for slots the kernels can address (`ok`).
+# ------------------------------------------------------------------------------------------------------------
+GRAD_IN_PLACE = True     # A/B switch (bench.py --set linear.GRAD_IN_PLACE=False: fresh tensors, gathered by pack())
+_SLOTS = {}              # id(parameter) -> (owner id, weakref to the parameter, flat buffer, offset, numel)
+_HANDED = set()          # ids of the parameters whose slot has been handed out since the last zero() / pack()
+
+
+def register_grad_slots(owner, params, flat: torch.Tensor, offsets) -> None:
+    """dp.FlatGradBuffer(views=False): parameter i's gradient belongs at flat[offsets[i] : offsets[i] + numel].  A later buffer
+    over the same parameter takes the entry over; `unregister_grad_slots` removes only the owner's own entries."""
+    import weakref
+    for p, o in zip(params, offsets):
+        _SLOTS[id(p)] = (id(owner), weakref.ref(p), flat, int(o), p.numel())
+
+
+def unregister_grad_slots(owner_id: int) -> None:
+    for k in [k for k, e in _SLOTS.items() if e[0] == owner_id]:
+        del _SLOTS[k]
+        _HANDED.discard(k)
+
+
+def reset_grad_slots(params=None) -> None:
+    """A new backward pass may take the slots again (FlatGradBuffer.zero / pack)."""
+    if params is None:
+        _HANDED.clear()
+    else:
+        _HANDED.difference_update(id(p) for p in params)
+
+
+def grad_slot_of(p: torch.Tensor) -> Optional[torch.Tensor]:
+    """A fresh view of the parameter's slot (None: not registered), whatever the switch says and without marking it handed out."""
+    e = _SLOTS.get(id(p))
+    if e is None or e[1]() is not p:
+        return None
+    return e[2][e[3]:e[3] + e[4]].view_as(p)
+
+
+def grad_slots(leaves, ok=None):
+    """Fresh slot views for ALL of `leaves` (leaf parameters, each asked for once), or None.  The caller has checked `all_steal`
+    for them.  `ok(views)`: the caller's own condition on the views (alignment, adjacency); nothing is marked when it fails."""
+    if not GRAD_IN_PLACE:
+        return None
+    leaves = list(leaves)
+    ids = [id(p) for p in leaves]
+    if len(set(ids)) != len(ids) or any(i in _HANDED for i in ids):
+        return None
+    views = []
+    for p in leaves:
+        v = grad_slot_of(p) if (p.is_leaf and p.is_cuda and p.grad is None and p.is_contiguous()) else None
+        if v is None:
+            return None
+        views.append(v)
+    if ok is not None and not ok(views):
+        return None
+    _HANDED.update(ids)
+    return views
+
+
+def slot_group(t: Optional[torch.Tensor]):
+    """In an op's FORWARD: the leaf parameters whose slots, taken together, hold this operand's gradient — the operand itself
+    when it is a leaf, the members of a row-wise cat / stack that is a view of adjacent parameters (params.cat_rows /
+    stack_rows mark it `_agnn_rowcat`); [] for no operand, None when its gradient has no such place."""
+    if t is None:
+        return []
+    if t.is_leaf:
+        return [t]
+    members = getattr(t, "_agnn_rowcat", None)      # its own attribute: `_agnn_leaves` is whatever mark_wgrad_async was told
+    return list(members) if members else None
+
+
+def grad_slot_groups(groups, shapes, ok=None):
+    """One view of `shapes[i]` over the slots of `groups[i]` (lists from `slot_group`), or None: a stacked or concatenated
+    gradient may be written in place only where its members' slots really lie back to back (params.adjacent).  An empty
+    group gives None in its place.  `ok(views)`: the caller's condition on the merged views."""
+    if any(g is None for g in groups):
+        return None
+    from .params import adjacent
+    merged = []
+
+    def build(views):
+        it = iter(views)
+        for g, shape in zip(groups, shapes):
+            vs = [next(it) for _ in g]
+            if not vs:
+                merged.append(None)
+                continue
+            n = 1
+            for d in shape:
+                n *= int(d)
+            if sum(v.numel() for v in vs) != n or (len(vs) > 1 and not adjacent(vs)):
+                return False
+            strides, acc = [], 1
+            for d in reversed(shape):
+                strides.append(acc)
+                acc *= int(d)
+            merged.append(vs[0].as_strided(tuple(int(d) for d in shape), tuple(reversed(strides)), vs[0].storage_offset()))
+        return ok is None or bool(ok(merged))
+    if grad_slots([p for g in groups for p in g], build) is None:
+        return None
+    return merged
+
+
 def _ok(t: torch.Tensor) -> bool:
     return (t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 2 == 0
             and t.shape[1] % 2 == 0 and t.data_ptr() % 8 == 0)
@@ -371,19 +482,38 @@ def weight_grad(dy: torch.Tensor, x: torch.Tensor, want_bias: bool, dw_out: Opti
 class WgItem:
     """One pending weight-gradient product dW = dY^T X (+ db) with its destinations: what a projection's backward leaves behind
     under dp.defer_weight_grads instead of a closure, so that the flush can issue all of them in one launch pair."""
-    __slots__ = ("dy", "x", "want_bias", "dw_out", "db_out", "event", "follows")
+    __slots__ = ("dy", "x", "want_bias", "dw_out", "db_out", "event", "follows", "dsts", "db_dsts")
 
-    def __init__(self, dy, x, want_bias, dw_out, db_out, follows=False):
+    def __init__(self, dy, x, want_bias, dw_out, db_out, follows=False, dsts=None, db_dsts=()):
         """`follows`: the second column block of the product whose first block is the item before it (`linear2`): the two count as
-        ONE product when groups are formed, so the launches are cut where they were cut with the input concatenated."""
+        ONE product when groups are formed, so the launches are cut where they were cut with the input concatenated.
+        `dsts` = [(c0, c1, matrix [out, c1 - c0])], `db_dsts` = [vector [out]] instead of `dw_out` / `db_out`: columns [c0, c1) of
+        the product go to every matrix that names them (`agnn_grad_epilogue_f32`), the bias gradient to every vector."""
         self.dy, self.x, self.want_bias, self.dw_out, self.db_out, self.event = dy, x, bool(want_bias), dw_out, db_out, None
         self.follows = bool(follows)
+        self.dsts, self.db_dsts = dsts, tuple(db_dsts)
 
     def tensors(self):
+        if self.dsts is not None:
+            return (self.dy, self.x, *[d for _, _, d in self.dsts], *self.db_dsts)
         return (self.dy, self.x, self.dw_out, self.db_out)
 
+    def destinations(self):
+        """([(c0, c1, matrix)], [vector]) whichever way the item was built."""
+        if self.dsts is not None:
+            return self.dsts, self.db_dsts
+        return [(0, self.x.shape[1], self.dw_out)], ((self.db_out,) if self.want_bias else ())
+
     def __call__(self):
-        weight_grad(self.dy, self.x, self.want_bias, dw_out=self.dw_out, db_out=self.db_out)
+        if self.dsts is None:
+            weight_grad(self.dy, self.x, self.want_bias, dw_out=self.dw_out, db_out=self.db_out)
+            return
+        # alone in its group, or not the batched kernel's: the single-product path (its own row slices) into temporaries, fanned
+        # out by one agnn_pack_f32 launch
+        from .params import pack
+        dw, db = weight_grad(self.dy, self.x, self.want_bias)
+        items = [(d, [dw[:, c0:c1]]) for c0, c1, d in self.dsts] + [(d.view(1, -1), [db.view(1, -1)]) for d in self.db_dsts]
+        pack(items, self.dy.device)
 
 
 class ColsumItem:
@@ -466,6 +596,90 @@ def weight_grad_batch(items) -> None:
         run(group)
 
 
+def _dst_ok(d: torch.Tensor, out_f: int, c0: int, c1: int) -> bool:
+    cols = c1 - c0
+    if d.dtype != torch.float32 or d.dim() != 2 or tuple(d.shape) != (out_f, cols) or d.stride(1) != 1 or d.stride(0) < cols:
+        return False
+    return d.data_ptr() % 4 == 0 if cols & 1 else (c0 % 2 == 0 and d.stride(0) % 2 == 0 and d.data_ptr() % 8 == 0)
+
+
+def grad_epilogue(items, sums) -> None:
+    """`weight_grad_batch` and `colsum_batch` on `agnn_grad_epilogue_f32`: the same groups of products (hence the same row slices
+    and sums), each group's slab sums stored to every destination of its items by one launch, which also carries the pending
+    column sums (with the last group).  A product alone in its group runs as it does in `weight_grad_batch`."""
+    lib = _lib.load()
+
+    def fits(it):
+        n, out_f = it.dy.shape
+        in_f = it.x.shape[1]
+        dsts, dbs = it.destinations()
+        return (ENABLED and it.dy.is_cuda and it.dy.dim() == 2 and it.x.dim() == 2 and n >= MIN_ROWS and out_f * in_f <= MAX_OUT_IN and in_f % 2 == 0
+                and _ok(it.dy) and _ok(it.x) and 0 < len(dsts) <= _lib.PACK_MAX_SRC and len(dbs) <= _lib.PACK_MAX_SRC
+                and all(d is not None and _dst_ok(d, out_f, c0, c1) for c0, c1, d in dsts) and bool(dbs) == it.want_bias
+                and all(d is not None and d.is_contiguous() and tuple(d.shape) == (out_f,) for d in dbs)
+                and (it.dsts is not None or all(d.data_ptr() % 8 == 0 for d in dbs)))       # (an item of the old kind: the old condition)
+
+    groups, group, products = [], [], 0
+    for it in items:
+        if fits(it):
+            joins = it.follows and group and group[-1].dy is it.dy
+            if group and ((products == _lib.WGRAD_BATCH_MAX and not joins) or len(group) == _lib.WGRAD_BATCH_MAX_ITEMS):
+                groups.append(group)
+                group, products, joins = [], 0, False
+            group.append(it)
+            products += 0 if joins else 1
+        else:
+            it()
+    if group:
+        groups.append(group)
+    sums = list(sums)
+    batched = [g for g in groups if len(g) > 1]
+    for g in groups:
+        if len(g) == 1:
+            g[0]()
+            continue
+        take, sums = (sums[:_lib.GRAD_MAX_SUMS], sums[_lib.GRAD_MAX_SUMS:]) if g is batched[-1] else ([], sums)
+        _epilogue_call(lib, g, take)
+    while sums:
+        _epilogue_call(lib, [], sums[:_lib.GRAD_MAX_SUMS])
+        sums = sums[_lib.GRAD_MAX_SUMS:]
+
+
+def _epilogue_call(lib, group, sums) -> None:
+    dev = (group[0].dy if group else sums[0].ws).device
+    arr = (_lib.GradItem * max(len(group), 1))()
+    for a, it in zip(arr, group):
+        dsts, dbs = it.destinations()
+        a.dy, a.x = it.dy.data_ptr(), it.x.data_ptr()
+        a.ld_dy, a.ld_x, a.n = it.dy.stride(0), it.x.stride(0), it.dy.shape[0]
+        a.out_f, a.in_f = it.dy.shape[1], it.x.shape[1]
+        a.n_dw, a.n_db = len(dsts), len(dbs)
+        for k, (c0, c1, d) in enumerate(dsts):
+            a.dw[k].p, a.dw[k].ld, a.dw[k].c0, a.dw[k].c1 = d.data_ptr(), (d.stride(0) if d.shape[0] > 1 else max(d.shape[1], d.stride(0))), c0, c1
+        for k, d in enumerate(dbs):
+            a.db[k] = d.data_ptr()
+    sarr = (_lib.ColsumItem * max(len(sums), 1))()
+    for a, it in zip(sarr, sums):
+        a.workspace, a.workspace_bytes, a.n, a.H = it.ws.data_ptr(), it.ws.numel(), it.n, it.H
+        a.dgamma, a.dbeta = it.dgamma.data_ptr(), it.dbeta.data_ptr()
+    nws = int(lib.agnn_grad_epilogue_workspace_bytes(len(group), arr)) if group else 0
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if group else None
+    _lib.check(lib.agnn_grad_epilogue_f32(len(group), arr, len(sums), sarr, _lib.ptr(ws), nws, _lib.stream_ptr(dev)), "agnn_grad_epilogue_f32")
+
+
+def _leaf_slots(groups, out_f: int, in_f: int, odd_ok: bool = False):
+    """(dw, db or None): the slots of a projection's weight (and bias) — its own leaves, or the adjacent parameters behind a
+    row-wise cat — as one [out, in] matrix and one [out] vector when they may be written in place, or None."""
+    if groups is None or not groups[0]:
+        return None
+
+    def ok(v):
+        dw, db = v
+        return (_dw_ok(dw) or (odd_ok and dw.shape[1] & 1 and dw.stride(1) == 1)) and (db is None or db.data_ptr() % 8 == 0)
+    v = grad_slot_groups(groups, ((out_f, in_f), (out_f,)), ok)
+    return None if v is None else (v[0], v[1])
+
+
 HAND_GEMM = True         # the forward projections on the hand-written fp32-MFMA kernel (csrc/gemm.hip, agnn_gemm_nt_f32); False (bench.py --set linear.HAND_GEMM=False): the library
 HAND_GEMM_DX = False     # ... and their input gradients dX = dY W (agnn_gemm_nn_f32: the weight K-major, as it lies).  Off: in the backward
                          # pass's contended window the TunableOp-chosen library kernels are faster (C2 step 2.87 vs 2.96 ms); bench.py --set linear.HAND_GEMM_DX=True
@@ -504,6 +718,13 @@ class _LinearFn(torch.autograd.Function):
         ctx.wg_async = _async_ok(w) and _async_ok(b)
         ctx.wg_defer = _deferrable(w) and _deferrable(b)
         ctx.steal_refs = leaf_refs(w, b)
+        # where the gradients finally belong: the leaves' own slots, or (a SAGE layer's operand, params.sage_operands_cat) the
+        # slots of the parameters behind the operand, named by its box
+        ctx.slot_groups = (slot_group(w), slot_group(b))
+        box = getattr(w, "_agnn_grad_box", None)
+        if box is not None:          # the one consumer the box allows takes the operand with the bias that belongs to it (or none)
+            box["uses"] += 1 if ((b is None and not box["b"]) or (b is not None and getattr(b, "_agnn_grad_box", None) is box)) else 2
+        ctx.grad_box = box
         ctx.grad_cols = getattr(x, "_agnn_grad_cols", None) if x.dim() == 2 else None     # (embedding.embed_cat: only these columns of dX are read)
         ctx.set_materialize_grads(False)          # an undefined output gradient (a structurally dead branch) stays undefined upstream
         if pre is not None:
@@ -529,19 +750,55 @@ class _LinearFn(torch.autograd.Function):
         if want_w and steals and ctx.wg_defer and (in_f % 2 == 0 or padded) and deferring(dy):
             # only dX stays here.  The closure fills aliases: a second reference to `dw` itself would make AccumulateGrad
             # CLONE it (now, before it is computed) instead of taking it over.
-            dw = torch.empty((dy.shape[1], in_f), dtype=torch.float32, device=dy.device)
-            db = torch.empty((dy.shape[1],), dtype=torch.float32, device=dy.device) if want_b else None
-            dw_k, db_k = dw.detach(), (db.detach() if db is not None else None)
-            if padded:                   # the product runs on in + 1 columns (models.encode's 281-wide note input); its first `in` are copied out
-                dw_wide = torch.empty((dy.shape[1], in_f + 1), dtype=torch.float32, device=dy.device)
-                defer(WgItem(dy, x.as_strided((x.shape[0], in_f + 1), (x.stride(0), 1), x.storage_offset()), want_b, dw_wide, db_k), dy.device, here=True)       # stays with its copy
-                defer(lambda: dw_k.copy_(dw_wide[:, :in_f]), dy.device)
+            box = ctx.grad_box
+            boxed = None
+            if box is not None and box["uses"] == 1 and not padded and ctx.needs_input_grad[1] and want_b == bool(box["b"]):
+                boxed = grad_slots(box["leaves"], lambda v: all((_dw_ok(t) if t.dim() == 2 else t.is_contiguous()) for t in v))
+            own = None
+            if boxed is None and ctx.needs_input_grad[1] and want_b == ctx.has_bias:
+                own = _leaf_slots(ctx.slot_groups, dy.shape[1], in_f, odd_ok=padded)
+            if boxed is not None:
+                # the operand's gradient is never materialised: the product stores its column blocks into the parameters' slots,
+                # the operand's backward hands those out.  What travels through autograd in its place only carries the shapes:
+                # zero-stride views of the resident 0.0, so that a hook or an anomaly check on the operand reads zeros, never
+                # uninitialised memory (params.sage_operands_cat states the invariant)
+                by = {id(p): v.detach() for p, v in zip(box["leaves"], boxed)}
+                box["slots"] = boxed
+                zero = resident.value(dy.device, ("grad_box_zero",), lambda: torch.zeros(1, dtype=torch.float32, device=dy.device), fill=True)
+                dw = zero.expand(dy.shape[1], in_f)
+                db = zero.expand(dy.shape[1]) if want_b else None
+                defer(WgItem(dy, x, want_b, None, None, dsts=[(c0, c1, by[id(p)]) for c0, c1, p in box["w"]],
+                             db_dsts=[by[id(p)] for p in box["b"]]), dy.device)
+                del boxed, by
             else:
-                defer(WgItem(dy, x, want_b, dw_k, db_k), dy.device)
+                if own is not None:
+                    dw, db = own
+                    del own
+                else:
+                    dw = torch.empty((dy.shape[1], in_f), dtype=torch.float32, device=dy.device)
+                    db = torch.empty((dy.shape[1],), dtype=torch.float32, device=dy.device) if want_b else None
+                dw_k, db_k = dw.detach(), (db.detach() if db is not None else None)
+                if padded and GRAD_IN_PLACE and BATCH:
+                    # the product runs on in + 1 columns (models.encode's 281-wide note input); the reduction stores the first `in`
+                    defer(WgItem(dy, x.as_strided((x.shape[0], in_f + 1), (x.stride(0), 1), x.storage_offset()), want_b, None, None,
+                                 dsts=[(0, in_f, dw_k)], db_dsts=([db_k] if want_b else [])), dy.device, here=True)
+                elif padded:             # ... or copied out behind it
+                    dw_wide = torch.empty((dy.shape[1], in_f + 1), dtype=torch.float32, device=dy.device)
+                    defer(WgItem(dy, x.as_strided((x.shape[0], in_f + 1), (x.stride(0), 1), x.storage_offset()), want_b, dw_wide, db_k), dy.device, here=True)       # stays with its copy
+                    defer(lambda: dw_k.copy_(dw_wide[:, :in_f]), dy.device)
+                else:
+                    defer(WgItem(dy, x, want_b, dw_k, db_k), dy.device)
         elif want_w:
             # forked before dX is queued: both start at once — only when the gradients will be STOLEN (no kernel on the main stream)
+            own = None
+            if steals and in_f % 2 == 0 and ctx.needs_input_grad[1] and want_b == ctx.has_bias and dy.is_cuda and dy.dim() == 2:
+                own = _leaf_slots(ctx.slot_groups, dy.shape[1], in_f)
             with wgrad_stream(dy.device, dy, x, active=steals):
-                dw, db = weight_grad(dy, x, want_b)
+                if own is not None:
+                    dw, db = weight_grad(dy, x, want_b, dw_out=own[0], db_out=own[1])
+                    del own
+                else:
+                    dw, db = weight_grad(dy, x, want_b)
         dx = None
         if ctx.needs_input_grad[0]:
             gc = ctx.grad_cols
@@ -607,6 +864,7 @@ class _Linear2Fn(torch.autograd.Function):
         ctx.wg_async = _async_ok(w) and _async_ok(b)
         ctx.wg_defer = _deferrable(w) and _deferrable(b)
         ctx.steal_refs = leaf_refs(w, b)
+        ctx.slot_groups = (slot_group(w), slot_group(b))
         ctx.set_materialize_grads(False)
         return hand_gemm2(x0, x1, w, b)
 
@@ -621,8 +879,13 @@ class _Linear2Fn(torch.autograd.Function):
         want_b = ctx.has_bias and ctx.needs_input_grad[3]
         steals = ctx.wg_async and all_steal(ctx.steal_refs)
         if want_w:
-            dw = torch.empty((dy.shape[1], w.shape[1]), dtype=torch.float32, device=dy.device)
-            db = torch.empty((dy.shape[1],), dtype=torch.float32, device=dy.device) if want_b else None
+            own = _leaf_slots(ctx.slot_groups, dy.shape[1], w.shape[1]) if (steals and ctx.needs_input_grad[2] and want_b == ctx.has_bias and k0 % 2 == 0) else None
+            if own is not None:
+                dw, db = own
+                del own
+            else:
+                dw = torch.empty((dy.shape[1], w.shape[1]), dtype=torch.float32, device=dy.device)
+                db = torch.empty((dy.shape[1],), dtype=torch.float32, device=dy.device) if want_b else None
             dw_k, db_k = dw.detach(), (db.detach() if db is not None else None)       # aliases: see _LinearFn.backward
             if steals and ctx.wg_defer and deferring(dy):
                 defer(WgItem(dy, x0, want_b, dw_k[:, :k0], db_k), dy.device)

@@ -472,6 +472,51 @@ typedef struct {
 } agnn_pack_item_t;
 int agnn_pack_f32(int32_t n_items, const agnn_pack_item_t* items /* (host) */, agnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Gradient epilogue: the products of agnn_wgrad_batch_f32 and the column sums of agnn_norm_act_colsum_batch_f32 with their
+ * results stored where they are finally wanted, in ONE reduction launch behind the product kernel.
+ *   * A product has up to AGNN_PACK_MAX_SRC weight destinations.  Record k receives columns [c0, c1) of dW: element (o, c) goes
+ *     to p[o * ld + (c - c0)].  Several records may name the same range (the summed root weight of a SAGE layer: one copy per
+ *     relation); columns that no record names are dropped (the spare column of an operand padded to an even width).  A record
+ *     with an even column count needs an even c0, an even ld and an 8-byte aligned p (stored as float2); one with an odd column
+ *     count is stored float by float (any ld >= its width).  `db[k]`, k < n_db: every one receives the bias gradient.
+ *   * Product kernel, tiles, row slices, slab layout and summation order are those of agnn_wgrad_batch_f32 on the same operand
+ *     list; a column sum has the bits of agnn_norm_act_colsum_f32.  No atomics.
+ *   * Destinations of one call must not overlap, except records of one product that name the same column range at the same
+ *     address with the same ld (they receive the same values): AGNN_EINVAL.  n_items <= 24, n_sums <= AGNN_GRAD_MAX_SUMS; both zero: AGNN_OK, nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+#define AGNN_GRAD_MAX_SUMS 16   /* column sums per agnn_grad_epilogue_f32 call */
+typedef struct {
+  float* p;          /* (device) element (0, c0) of the destination */
+  int64_t ld;
+  int32_t c0, c1;
+} agnn_grad_dst_t;
+typedef struct {
+  const float* dy;   /* operand fields: as agnn_wgrad_item_t */
+  const float* x;
+  int64_t ld_dy, ld_x, n;
+  int32_t out_f, in_f;
+  int32_t n_dw, n_db;
+  agnn_grad_dst_t dw[AGNN_PACK_MAX_SRC];
+  float* db[AGNN_PACK_MAX_SRC];
+} agnn_grad_item_t;
+size_t agnn_grad_epilogue_workspace_bytes(int32_t n_items, const agnn_grad_item_t* items /* (host) */);
+int agnn_grad_epilogue_f32(int32_t n_items, const agnn_grad_item_t* items /* (host) */, int32_t n_sums,
+                           const agnn_colsum_item_t* sums /* (host) */, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+
+/* Many contiguous pieces copied (src != NULL) or zero-filled (src == NULL) in one launch per AGNN_GATHER_MAX_ITEMS pieces:
+ * what dp.FlatGradBuffer.pack has left to do once the producers write their gradients in place — the remaining gradients into
+ * their slots of the flat buffer, the slots of parameters without a gradient cleared.  Plainer items than agnn_pack_f32's (no
+ * sums, no strides), so that a whole model's remainder fits one kernel argument.  n < 2^31 floats per piece; pieces of one call
+ * must not overlap.  Items are read on the host during the call. */
+#define AGNN_GATHER_MAX_ITEMS 128
+typedef struct {
+  float* dst;          /* (device) */
+  const float* src;    /* (device) or NULL */
+  int64_t n;
+} agnn_gather_item_t;
+int agnn_gather_f32(int32_t n_items, const agnn_gather_item_t* items /* (host) */, agnn_stream_t stream);
+
 /* Measurement aid (scripts/step_stamps.py): one single-lane kernel that stores the constant-rate 100 MHz counter
  * (s_memrealtime) into *slot when the stream reaches it — a time stamp that can be captured into a hipGraph and read back
  * after the replay, without a profiler attached.  Not used by the product path. */
