@@ -126,6 +126,23 @@ class LrSchedule(C.Structure):
                 ("decay_steps", C.c_double), ("swa_lr", C.c_double)]
 
 
+JK_MAX_T = 8                  # AGNN_JK_MAX_T
+
+
+class LstmStep(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("ld_x", C.c_int64), ("hprev", C.c_void_p), ("ld_hprev", C.c_int64), ("cprev", C.c_void_p),
+                ("ld_cprev", C.c_int64), ("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p),
+                ("hout", C.c_void_p), ("ld_hout", C.c_int64), ("cout", C.c_void_p), ("ld_cout", C.c_int64), ("act", C.c_void_p),
+                ("att_w", C.c_void_p), ("part", C.c_void_p), ("M", C.c_int64), ("K0", C.c_int32), ("h", C.c_int32)]
+
+
+class LstmCellBwd(C.Structure):
+    _fields_ = [("act", C.c_void_p), ("c", C.c_void_p), ("ld_c", C.c_int64), ("cprev", C.c_void_p), ("ld_cprev", C.c_int64),
+                ("dh", C.c_void_p), ("ld_dh", C.c_int64), ("dc_next", C.c_void_p), ("ld_dc_next", C.c_int64), ("dscore", C.c_void_p),
+                ("ld_dscore", C.c_int64), ("att_w", C.c_void_p), ("dgates", C.c_void_p), ("dc_prev", C.c_void_p),
+                ("ld_dc_prev", C.c_int64), ("wpart", C.c_void_p), ("M", C.c_int64), ("h", C.c_int32)]
+
+
 _lib: Optional[C.CDLL] = None
 
 # every exported symbol of include/agnn.h: (name, restype, argtypes)
@@ -266,6 +283,14 @@ SIGNATURES = {
     "agnn_eval_counts_len": (C.c_size_t, [C.c_int32, C.c_int32]),
     "agnn_multitask_eval_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                           C.c_int64, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "agnn_lstm_step_f32": (C.c_int, [C.c_int32, C.POINTER(LstmStep), C.c_void_p]),
+    "agnn_jk_combine_fwd_f32": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "agnn_jk_combine_bwd_f32": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]),
+    "agnn_lstm_cell_bwd_row_blocks": (C.c_int64, [C.c_int64]),
+    "agnn_lstm_cell_bwd_f32": (C.c_int, [C.c_int32, C.POINTER(LstmCellBwd), C.c_void_p]),
+    "agnn_colsum_parts_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -253,7 +253,8 @@ class HeteroSageConvLayer(nn.Module):
 
 
 class JumpingKnowledge(nn.Module):
-    """core/gnn.py:345-365: bi-LSTM attention over the per-layer outputs (MIOpen LSTM)."""
+    """core/gnn.py:345-365: bi-LSTM attention over the per-layer outputs — on the kernels of csrc/lstm.hip where
+    `jk.kernel_applicable` holds (analysisgnn_amd/jk.py), on the library LSTM (MIOpen) otherwise."""
 
     def __init__(self, n_hidden, n_layers):
         super().__init__()
@@ -266,6 +267,9 @@ class JumpingKnowledge(nn.Module):
         nn.init.xavier_uniform_(self.att.weight, gain=nn.init.calculate_gain("relu"))
 
     def forward(self, xs):
+        from . import jk
+        if jk.FUSED and jk.kernel_applicable(self, xs):      # csrc/lstm.hip; otherwise the library body below, unchanged
+            return jk.jumping_knowledge(self, xs)
         x = torch.stack(xs, dim=1)
         alpha, _ = self.lstm(x)
         alpha = torch.softmax(self.att(alpha).squeeze(-1), dim=-1)

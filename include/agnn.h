@@ -899,6 +899,74 @@ int agnn_multitask_eval_f32(const float* logits, int64_t ld, const int32_t* seg_
                             const uint8_t* row_mask, int32_t gate_task, uint32_t group_mask, int32_t* pred, int64_t* counts,
                             agnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * JumpingKnowledge (ref: models/core/gnn.py:345-365) — a bidirectional LSTM over the T layer outputs of every row, an attention
+ * score per layer, a softmax over the layers and the weighted sum of the layer outputs.  fp32, no atomics: every cross-tile sum
+ * goes through a partials buffer summed in a fixed order (two runs give the same bits).  analysisgnn_amd/jk.py orders the calls.
+ *
+ * agnn_lstm_step_f32: ONE time step of one or two directions (n_items <= 2, same M, K0, h, both first steps or both later ones):
+ *     g = x[M, K0] W_ih[4h, K0]^T + hprev[M, h] W_hh[4h, h]^T + b_ih + b_hh      (gate order i, f, g, o: PyTorch's row blocks)
+ *     cout = sigmoid(f) cprev + sigmoid(i) tanh(g) ,   hout = sigmoid(o) tanh(cout)
+ *   on the tile of agnn_gemm_nt2_f32 with the cell in its epilogue.  The weights and biases are contiguous and read where they
+ *   lie.  hprev == NULL: the first step (h = c = 0; no recurrent product, cprev not read).  act != NULL: the post-nonlinearity
+ *   gates act[M, 4h] (ld 4h) are written for the backward.  att_w != NULL (this direction's h entries of att.weight):
+ *   part[m, j] = sum_{u in [32 j, 32 j + 32)} att_w[u] hout[m, u], part [M, h / 32] contiguous.
+ *   K0 % 16 == 0, h % 32 == 0; x, hprev and the weights 16-byte aligned with ld % 4 == 0.
+ * agnn_jk_combine_fwd_f32: score[m, t] = sum_d sum_j part[d][t][m][j] (part [n_dir, T, M, n_tiles], summed in that order),
+ *   alpha[m, :] = softmax_t(score) (written, [M, T]), out[m, :] = sum_t alpha[m, t] x_t[m, :].  The T <= AGNN_JK_MAX_T inputs are
+ *   read through a host list of pointers with their leading dimensions.  att.bias shifts every score of a row alike and cancels
+ *   in the softmax: it is not an argument.
+ * agnn_jk_combine_bwd_f32: dalpha_t = dout . x_t, dscore[m, t] = alpha_t (dalpha_t - sum_s alpha_s dalpha_s) ([M, T]), and the
+ *   direct term dx_t = alpha_t dout into dxs[t].
+ * agnn_lstm_cell_bwd_f32: the pointwise backward of one step (1 - 2 items).  dh = dh (NULL at the last step) + dscore[m] att_w
+ *   (rank one, never materialised), dc = dc_next (NULL at the last step) + dh o (1 - tanh^2 c); dgates[M, 4h] (pre-activation,
+ *   ld 4h) and dc_prev = dc f (NULL: not wanted); cprev == NULL at the first step (c_{-1} = 0).  wpart[b, u] = sum over the rows
+ *   of row block b (agnn_lstm_cell_bwd_row_blocks(M) blocks) of dscore[m] h[m, u] with h = o tanh(c) recomputed: the partials of
+ *   att.weight's gradient, summed by agnn_colsum_parts_f32 (out[c] = sum_r parts[r, c], fixed order).  h % 4 == 0, 16-byte
+ *   aligned operands.
+ * ------------------------------------------------------------------------------------------ */
+#define AGNN_JK_MAX_T 8
+typedef struct {
+  const float* x;       int64_t ld_x;
+  const float* hprev;   int64_t ld_hprev;
+  const float* cprev;   int64_t ld_cprev;
+  const float* w_ih;    /* [4h, K0] */
+  const float* w_hh;    /* [4h, h] */
+  const float* b_ih;    /* [4h] */
+  const float* b_hh;    /* [4h] */
+  float* hout;          int64_t ld_hout;
+  float* cout;          int64_t ld_cout;
+  float* act;           /* [M, 4h] or NULL */
+  const float* att_w;   /* [h] or NULL */
+  float* part;          /* [M, h / 32] */
+  int64_t M;
+  int32_t K0, h;
+} agnn_lstm_step_t;
+int agnn_lstm_step_f32(int32_t n_items, const agnn_lstm_step_t* items /* (host) */, agnn_stream_t stream);
+int agnn_jk_combine_fwd_f32(int32_t T, const float* const* xs /* (host) */, const int64_t* ld_xs /* (host) */, int64_t M, int32_t H,
+                            const float* part, int32_t n_dir, int32_t n_tiles, float* alpha, float* out, int64_t ld_out,
+                            agnn_stream_t stream);
+int agnn_jk_combine_bwd_f32(int32_t T, const float* const* xs /* (host) */, const int64_t* ld_xs /* (host) */, int64_t M, int32_t H,
+                            const float* alpha, const float* dout, int64_t ld_dout, float* dscore, float* const* dxs /* (host) */,
+                            const int64_t* ld_dxs /* (host) */, agnn_stream_t stream);
+typedef struct {
+  const float* act;      /* [M, 4h] */
+  const float* c;        int64_t ld_c;
+  const float* cprev;    int64_t ld_cprev;
+  const float* dh;       int64_t ld_dh;
+  const float* dc_next;  int64_t ld_dc_next;
+  const float* dscore;   int64_t ld_dscore;     /* dscore[m * ld_dscore] */
+  const float* att_w;    /* [h] */
+  float* dgates;         /* [M, 4h] */
+  float* dc_prev;        int64_t ld_dc_prev;
+  float* wpart;          /* [row blocks, h] */
+  int64_t M;
+  int32_t h;
+} agnn_lstm_cell_bwd_t;
+int64_t agnn_lstm_cell_bwd_row_blocks(int64_t M);
+int agnn_lstm_cell_bwd_f32(int32_t n_items, const agnn_lstm_cell_bwd_t* items /* (host) */, agnn_stream_t stream);
+int agnn_colsum_parts_f32(const float* parts, int64_t n_rows, int32_t n_cols, float* out, agnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
