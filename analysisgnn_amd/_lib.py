@@ -291,6 +291,13 @@ SIGNATURES = {
     "agnn_lstm_cell_bwd_row_blocks": (C.c_int64, [C.c_int64]),
     "agnn_lstm_cell_bwd_f32": (C.c_int, [C.c_int32, C.POINTER(LstmCellBwd), C.c_void_p]),
     "agnn_colsum_parts_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "agnn_attn_fwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                    C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "agnn_attn_bwd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "agnn_attn_bwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                    C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "agnn_attn_dropout_keep_f32": (C.c_int, [C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
 

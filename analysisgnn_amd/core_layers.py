@@ -753,3 +753,118 @@ class MetricalGNN(nn.Module):
         if self.use_metrical:
             h, h_beat, h_measure = metrical(len(self.beat_convs) - 1, h, h_beat, h_measure)
         return self.convs[-1](h, edge_index, edge_type)
+
+
+# ------------------------------------------------------------------------------------------
+# Graph-transformer branch (core/gnn.py:426-485 GPSLayer, core/hgnn.py:220-320 HGPSLayer / HGPS): a local edge-gated
+# convolution and GLOBAL self-attention over all rows of the batch (analysisgnn_amd/attention.py, csrc/attn.hip), each followed
+# by activation -> LayerNorm -> dropout and a residual, then a two-layer feed-forward block and an L2 normalisation.
+# ------------------------------------------------------------------------------------------
+def _is_relu(act) -> bool:
+    return act is F.relu or act is torch.relu or isinstance(act, nn.ReLU)
+
+
+class _GPSBlock(nn.Module):
+    """What GPSLayer and HGPSLayer share: everything after the local convolution."""
+
+    def _act_norm_drop(self, h, ln: nn.LayerNorm, drop: nn.Dropout):
+        from . import fused
+        if _is_relu(self.activation):
+            return fused.norm_act(h, ln, pre_relu=True, p=drop.p, training=self.training)
+        return drop(ln(self.activation(h)))
+
+    def _combine(self, h_init, local_out):
+        from . import attention, fused, linear
+        local_out = self._act_norm_drop(local_out, self.normalize_local, self.dropout_local) + h_init
+        attn_out = attention.self_attention(self.attn, h_init, self.training)
+        attn_out = self._act_norm_drop(attn_out, self.normalize_attn, self.dropout_attn) + h_init
+        out = local_out + attn_out
+        h = linear.linear(out, self.ff1.weight, self.ff1.bias)
+        if _is_relu(self.activation):      # relu -> dropout in one launch, the mask from the library's own generator (follows capture)
+            h = fused.skip_act(h, None, None, True, self.dropout_ff.p, self.training)
+        else:
+            h = self.dropout_ff(self.activation(h))
+        h = linear.linear(h, self.ff2.weight, self.ff2.bias)
+        # the reference's `h - self.dropout_ff(h)` (gnn.py:483, hgnn.py:285) is a statement without effect; its mask is not drawn here
+        return F.normalize(out + h)
+
+    def _make_block(self, out_features, num_heads, dropout, bias):
+        self.normalize_local = nn.LayerNorm(out_features)
+        self.normalize_attn = nn.LayerNorm(out_features)
+        self.dropout_ff = nn.Dropout(dropout)
+        self.dropout_attn = nn.Dropout(dropout)
+        self.dropout_local = nn.Dropout(dropout)
+        self.ff1 = nn.Linear(out_features, out_features * 2, bias=bias)
+        self.ff2 = nn.Linear(out_features * 2, out_features, bias=bias)
+        # the parameter holder of attention.self_attention: its forward is never called
+        self.attn = nn.MultiheadAttention(out_features, num_heads, dropout=dropout, bias=bias, batch_first=True)
+
+
+class GPSLayer(_GPSBlock):
+    """core/gnn.py:426-485.  The residuals add the input itself, so in_features == out_features.  Attention is global over
+    the rows of x (one unbatched sequence, no mask), as in the reference."""
+
+    def __init__(self, in_features, out_features, num_heads, activation, dropout=0.2, bias=True):
+        super().__init__()
+        self.in_features, self.out_features, self.num_heads = in_features, out_features, num_heads
+        self.activation = activation
+        self._make_block(out_features, num_heads, dropout, bias)
+        self.local = ResGatedGraphConv(in_features, out_features, bias=bias)
+
+    def forward(self, x, edge_index):
+        _lib.require_gpu(x)
+        return self._combine(x, self.local(x, edge_index))
+
+
+class HGPSLayer(_GPSBlock):
+    """core/hgnn.py:220-287: GPSLayer behind an input embedding, with the hetero edge-gated convolution (mean over the
+    relations) as the local branch."""
+
+    def __init__(self, in_features, out_features, num_heads, etypes=None, activation=F.relu, dropout=0.2, bias=True):
+        super().__init__()
+        etypes = dict(_DEFAULT_ETYPES) if etypes is None else etypes
+        self.embedding = nn.Linear(in_features, out_features, bias=bias)
+        self.in_features, self.out_features, self.num_heads = in_features, out_features, num_heads
+        self.activation = activation
+        self._make_block(out_features, num_heads, dropout, bias)
+        self.local = HeteroResGatedGraphConvLayer(out_features, out_features, bias=bias, etypes=etypes)
+
+    def forward(self, x, edge_index, edge_type):
+        from . import linear
+        _lib.require_gpu(x)
+        h_init = linear.linear(x, self.embedding.weight, self.embedding.bias)
+        return self._combine(h_init, self.local(h_init, edge_index, edge_type))
+
+
+class HGPS(nn.Module):
+    """core/hgnn.py:290-320: n_layers + 1 HGPSLayers of 4 heads, ALL inside the loop, each followed by
+    activation -> L2 normalise -> dropout (the last one too); with jk=True the JumpingKnowledge sees n_layers + 1 inputs
+    (which needs out_feats == n_hidden).  The layers keep their own dropout default (0.2) whatever `dropout` says."""
+
+    def __init__(self, in_feats, n_hidden, out_feats, n_layers, etypes=None, activation=F.relu, dropout=0.5, jk=False):
+        super().__init__()
+        etypes = dict(_DEFAULT_ETYPES) if etypes is None else etypes
+        self.n_hidden = n_hidden
+        self.layers = nn.ModuleList()
+        self.normalize = F.normalize
+        self.activation = activation
+        self.dropout = nn.Dropout(dropout)
+        self.layers.append(HGPSLayer(in_feats, n_hidden, etypes=etypes, num_heads=4))
+        for _ in range(n_layers - 1):
+            self.layers.append(HGPSLayer(n_hidden, n_hidden, etypes=etypes, num_heads=4))
+        self.use_knowledge = bool(jk)
+        if jk:
+            self.jk = JumpingKnowledge(n_hidden=n_hidden, n_layers=n_layers)
+        self.layers.append(HGPSLayer(n_hidden, out_feats, etypes=etypes, num_heads=4))
+
+    def forward(self, x, edge_index, edge_type):
+        from . import fused
+        h, hs = x, []
+        for conv in self.layers:
+            h = self.normalize(self.activation(conv(h, edge_index, edge_type)))
+            # the stack's dropout on the library's generator too (one launch; widths off 4 floats fall back to torch's inside)
+            h = fused.skip_act(h, None, None, False, self.dropout.p, self.training)
+            hs.append(h)
+        if self.use_knowledge:
+            h = self.jk(hs)
+        return h

@@ -71,6 +71,20 @@ __device__ __forceinline__ float wave_max_dpp(float v) {
   v = fmaxf(v, dpp_mov<0x140>(v));
   return fmaxf(fmaxf(lane_value(v, 0), lane_value(v, 16)), fmaxf(lane_value(v, 32), lane_value(v, 48)));
 }
+
+// Philox-4x32-10 (Salmon et al. 2011): 4 x 32 random bits for counter (c0..c3), key (k0,k1).  The project's dropout masks:
+// counter = (element index lo, hi, call id, training step lo), key = (seed lo, seed hi ^ step hi).
+__device__ __forceinline__ uint4 philox(uint4 c, uint2 k) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c.x), l0 = 0xD2511F53u * c.x;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c.z), l1 = 0xCD9E8D57u * c.z;
+    c = make_uint4(h1 ^ c.y ^ k.x, l1, h0 ^ c.w ^ k.y, l0);
+    k.x += 0x9E3779B9u;
+    k.y += 0xBB67AE85u;
+  }
+  return c;
+}
 #endif
 
 // wgrad.hip: fixed-order sum of S partial-result slabs (used by the weight-gradient kernels)

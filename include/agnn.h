@@ -967,6 +967,36 @@ int64_t agnn_lstm_cell_bwd_row_blocks(int64_t M);
 int agnn_lstm_cell_bwd_f32(int32_t n_items, const agnn_lstm_cell_bwd_t* items /* (host) */, agnn_stream_t stream);
 int agnn_colsum_parts_f32(const float* parts, int64_t n_rows, int32_t n_cols, float* out, agnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Dense multi-head self-attention over the N rows of a batch (ref: nn.MultiheadAttention as GPSLayer / HGPSLayer call it,
+ * models/core/gnn.py:471, core/hgnn.py:273: one unbatched sequence, no mask), exact fp32, flash style: nothing of size N x N
+ * is written.  q, k, v: [N, heads D] column blocks with ONE row stride ld_qkv (the three blocks of the in-projection's
+ * [N, 3E] output where they lie).  D in {8, 16, 32, 64}, heads >= 1, N >= 1; anything else is AGNN_EINVAL before any HIP call.
+ * All rows 16-byte aligned (AGNN_EALIGN).  q_rows: query rows per workgroup, 0 (chosen from N and heads), 64 or 128.
+ *
+ * agnn_attn_fwd_f32:  P = softmax(scale q k^T) per head, o = (P o keep) v with the heads side by side ([N, heads D], ld_o),
+ *   lse[heads, N] = log sum exp of the scaled scores.  Dropout p acts on the normalised probabilities as torch's does: keep is
+ *   0 or 1 / (1 - p), drawn by the project's counter-based generator from (rng_state[0] = seed, rng_state[1] = step, call_id);
+ *   one draw serves keys 4g .. 4g + 3 of a query row, its counter is the 64-bit element index (head N + query) N + 4g.
+ *   With p > 0 the (seed, step) read is copied to rng_used (device int64[2]) for the backward.  p == 0: neither is touched.
+ * agnn_attn_bwd_f32:  dq, dk, dv ([N, heads D] column blocks with one row stride ld_dqkv: the in-projection's dY) from dO, o,
+ *   lse and the forward's inputs; P is recomputed; rng_used is the forward's.  dq is formed in a pass of its own over the query
+ *   rows (S is computed twice): no atomics, no workgroup waits for another, and two runs give the same bits.
+ *   workspace: agnn_attn_bwd_workspace_bytes(N, heads) bytes, 16-byte aligned (the row sums of dO o o).
+ * agnn_attn_dropout_keep_f32:  the keep factors of (rng, call_id) as a dense [heads, N, N] matrix (all ones at p == 0), by the
+ *   device function the two kernels use: for inspection and tests, N <= 8192.
+ * ------------------------------------------------------------------------------------------ */
+int agnn_attn_fwd_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, int64_t N, int32_t heads, int32_t D, float scale,
+                      float p, const int64_t* rng_state, uint32_t call_id, int32_t q_rows, float* o, int64_t ld_o, float* lse,
+                      int64_t* rng_used, agnn_stream_t stream);
+size_t agnn_attn_bwd_workspace_bytes(int64_t N, int32_t heads);
+int agnn_attn_bwd_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, int64_t N, int32_t heads, int32_t D, float scale,
+                      float p, const int64_t* rng_used, uint32_t call_id, int32_t q_rows, const float* dO, int64_t ld_do,
+                      const float* o, int64_t ld_o, const float* lse, float* dq, float* dk, float* dv, int64_t ld_dqkv,
+                      void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+int agnn_attn_dropout_keep_f32(int64_t N, int32_t heads, float p, const int64_t* rng, uint32_t call_id, float* keep,
+                               agnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
