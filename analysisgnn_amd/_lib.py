@@ -298,6 +298,12 @@ SIGNATURES = {
                                     C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "agnn_attn_dropout_keep_f32": (C.c_int, [C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "agnn_taskattn_fwd_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p,
+                                        C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "agnn_taskattn_bwd_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p,
+                                        C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_void_p]),
+    "agnn_taskattn_dropout_keep_f32": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -254,7 +254,9 @@ class CrossTaskTransformer(nn.Module):
     (batch_first, `num_heads` heads, dropout on the attention probabilities).  Same parameters and names
     (`multihead_attn.in_proj_weight / in_proj_bias / out_proj.*`, `norm.*`); the schedule differs: the packed in-projection
     and the out-projection are single [N*T, E] GEMMs on `linear` (weight gradients on the split-N MFMA kernel), the
-    T x T attention of all notes and heads is one scaled-dot-product call, and residual + LayerNorm is one fused launch."""
+    T x T attention of all notes and heads is one launch of csrc/taskattn.hip on the in-projection as it lies (`task_attention`),
+    and residual + LayerNorm is one fused launch.  Shapes the kernel does not serve (head width outside {8, 16, 32}, more than 32
+    tasks, non-fp32 input) and `task_attention.FUSED = False` run the library's scaled-dot-product call on transposed views."""
 
     def __init__(self, proj_dim, num_heads=4, dropout=0.1):
         super().__init__()
@@ -262,15 +264,21 @@ class CrossTaskTransformer(nn.Module):
         self.norm = nn.LayerNorm(proj_dim)
 
     def forward(self, task_projections):
+        from . import task_attention
         from .fused import norm_act
         mha = self.multihead_attn
         N, T, E = task_projections.shape
         h = mha.num_heads
+        p = mha.dropout if self.training else 0.0
         x2 = task_projections.reshape(N * T, E)
-        qkv = linear(x2, mha.in_proj_weight, mha.in_proj_bias).view(N, T, 3, h, E // h)
-        q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))                      # [N, h, T, E/h]
-        att = F.scaled_dot_product_attention(q, k, v, dropout_p=mha.dropout if self.training else 0.0)
-        att = att.transpose(1, 2).reshape(N * T, E)
+        qkv = linear(x2, mha.in_proj_weight, mha.in_proj_bias)                           # [N*T, 3E]
+        if task_attention.FUSED and task_attention.kernel_applicable(N, T, h, E, qkv.dtype, qkv.device):
+            att = task_attention.attention(qkv, T, h, p)                                 # [N*T, E], heads side by side
+        else:
+            qkv = qkv.view(N, T, 3, h, E // h)
+            q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))                  # [N, h, T, E/h]
+            att = F.scaled_dot_product_attention(q, k, v, dropout_p=p)
+            att = att.transpose(1, 2).reshape(N * T, E)
         out = linear(att, mha.out_proj.weight, mha.out_proj.bias, acc=x2)                # residual as the GEMM's beta = 1 epilogue
         return norm_act(out, self.norm).view(N, T, E)
 

@@ -35,6 +35,7 @@
  *   agnn_relt_*           PyG `HGTConv` per-head relation transforms (k_rel / v_rel)
  *   agnn_hgt_attn_*       PyG `HGTConv` message/softmax/aggregate, reached through graphmuse
  *                         `HybridHGT` (ref: models/analysis.py:445-453)
+ *   agnn_taskattn_*       `CrossTaskTransformer`: attention over the task tokens of every note (ref: models/analysis.py:408-418)
  *
  * Conventions (all entry points)
  *   - plain pointers and sizes only; every `const T*`/`T*` marked (device) is device memory owned
@@ -996,6 +997,36 @@ int agnn_attn_bwd_f32(const float* q, const float* k, const float* v, int64_t ld
                       void* workspace, size_t workspace_bytes, agnn_stream_t stream);
 int agnn_attn_dropout_keep_f32(int64_t N, int32_t heads, float p, const int64_t* rng, uint32_t call_id, float* keep,
                                agnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Cross-task attention of the logit-fusion block (ref: CrossTaskTransformer, models/analysis.py:408-418): n_seq independent
+ * sequences of T tokens, exact fp32, one lane per (sequence, head, row); nothing of size n_seq x heads x T x T is written.
+ * qkv: the packed in-projection [n_seq T, 3E] with row stride ld_qkv, row n T + t = token t of sequence n, columns q | k | v,
+ * head h in columns h D .. h D + D - 1 of each block (E = heads D).  o: [n_seq T, E], the heads side by side.  dqkv: [n_seq T, 3E],
+ * written completely.  D in {8, 16, 32}, 1 <= T <= AGNN_MAX_SEG, heads >= 1 with heads D <= 128 and heads T <= 256, n_seq >= 0,
+ * p in [0, 1): anything else is AGNN_EINVAL before any HIP call, as are NULL pointers, leading dimensions below 3E (E for o / dO)
+ * and p > 0 without its state; a pointer off 16 bytes or a leading dimension that is no multiple of 4 floats is AGNN_EALIGN.
+ * n_seq == 0 returns AGNN_OK and looks at no pointer.
+ *
+ * agnn_taskattn_fwd_f32:  P = softmax(scale q k^T) over the T keys per (sequence, head), o = (P o keep) v.  lse (optional, NULL:
+ *   not written): [n_seq T, heads], log2 of the sum of exp2 of the scores in log2 units (scale log2(e) q k^T): what the backward
+ *   reads.  Dropout p acts on the normalised probabilities as torch's does: keep is 0 or 1 / (1 - p), drawn by the project's
+ *   counter-based generator from (rng_state[0] = seed, rng_state[1] = step, call_id); one draw serves keys 4g .. 4g + 3 of a
+ *   query row, its counter is the element index ((n heads + h) 32 + i) 32 + 4g.  With p > 0 the (seed, step) read is copied to
+ *   rng_used (device int64[2]); at p == 0 nothing is drawn and neither is touched (both may be NULL).
+ * agnn_taskattn_bwd_f32:  dqkv from dO, the forward's qkv, o and lse; P is recomputed (twice: once query-major for dq, once
+ *   key-major for dk and dv), the masks are redrawn from rng_used.  No atomics; two runs give the same bits.
+ * agnn_taskattn_dropout_keep_f32:  the keep factors of (rng, call_id) as a dense [n_seq, heads, T, T] tensor (all ones at
+ *   p == 0), by the device function the two kernels use: for inspection and tests.
+ * ------------------------------------------------------------------------------------------ */
+int agnn_taskattn_fwd_f32(const float* qkv, int64_t ld_qkv, int64_t n_seq, int32_t T, int32_t heads, int32_t D, float scale, float p,
+                          const int64_t* rng_state, uint32_t call_id, float* o, int64_t ld_o, float* lse, int64_t* rng_used,
+                          agnn_stream_t stream);
+int agnn_taskattn_bwd_f32(const float* qkv, int64_t ld_qkv, int64_t n_seq, int32_t T, int32_t heads, int32_t D, float scale, float p,
+                          const int64_t* rng_used, uint32_t call_id, const float* dO, int64_t ld_do, const float* o, int64_t ld_o,
+                          const float* lse, float* dqkv, int64_t ld_dqkv, agnn_stream_t stream);
+int agnn_taskattn_dropout_keep_f32(int64_t n_seq, int32_t T, int32_t heads, float p, const int64_t* rng, uint32_t call_id,
+                                   float* keep /* [n_seq, heads, T, T] */, agnn_stream_t stream);
 
 #ifdef __cplusplus
 }
