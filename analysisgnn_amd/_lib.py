@@ -143,6 +143,15 @@ class LstmCellBwd(C.Structure):
                 ("ld_dc_prev", C.c_int64), ("wpart", C.c_void_p), ("M", C.c_int64), ("h", C.c_int32)]
 
 
+ROWSEL_MAX_K = 8              # AGNN_ROWSEL_MAX_K
+ROWSEL_COSINE, ROWSEL_SQDIST = 0, 1
+
+
+class SmotePlan(C.Structure):
+    _fields_ = [("n_seg", C.c_int32), ("t_off", C.c_int32 * (MAX_SEG + 1)), ("s_off", C.c_int32 * (MAX_SEG + 1)),
+                ("copies", C.c_int32 * MAX_SEG), ("label", C.c_int64 * MAX_SEG)]
+
+
 _lib: Optional[C.CDLL] = None
 
 # every exported symbol of include/agnn.h: (name, restype, argtypes)
@@ -304,6 +313,15 @@ SIGNATURES = {
                                         C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                         C.c_void_p]),
     "agnn_taskattn_dropout_keep_f32": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "agnn_rowsel_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "agnn_smote_synth_fwd_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(SmotePlan), C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "agnn_smote_synth_bwd_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(SmotePlan), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "agnn_smote_draws_f32": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

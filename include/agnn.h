@@ -1028,6 +1028,55 @@ int agnn_taskattn_bwd_f32(const float* qkv, int64_t ld_qkv, int64_t n_seq, int32
 int agnn_taskattn_dropout_keep_f32(int64_t n_seq, int32_t T, int32_t heads, float p, const int64_t* rng, uint32_t call_id,
                                    float* keep /* [n_seq, heads, T, T] */, agnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SMOTE oversampling of the minority classes and the nearest-original search of its feature penalty (ref:
+ * models/cadence.py:13-118 `SMOTE`, models/analysis.py:1412-1438 `update_feature_loss`; csrc/smote.hip).
+ * D % 4 == 0 and 4 <= D <= 512, rows 16-byte aligned, leading dimensions multiples of 4 floats: AGNN_EINVAL / AGNN_EALIGN
+ * before any HIP call otherwise, as for NULL pointers.  No float atomics: two runs give the same bits.
+ *
+ * agnn_rowsel_f32:  for every query row the ksel (1 .. AGNN_ROWSEL_MAX_K) smallest scores among the candidate rows of its own
+ *   segment, ascending, ties to the lower index.  Query p of segment s (q_off[s] <= p < q_off[s + 1], HOST arrays of
+ *   n_seg + 1 <= AGNN_MAX_SEG + 1 ascending offsets, read during the call) is row q_rows[p] of q (p itself with q_rows NULL);
+ *   candidates likewise from c, c_rows, c_off.  q_n / c_n: rows of q / c; a row index outside them makes the row NaN, and a NaN
+ *   score is never selected.  Scores: AGNN_ROWSEL_COSINE  q.c / (max(|q|, 1e-12) max(|c|, 1e-12))  (the similarity of
+ *   F.normalize'd rows; the SMALLEST similarities are selected), AGNN_ROWSEL_SQDIST  sum (q - c)^2  summed from the differences.
+ *   idx [Q, ksel] holds candidate POSITIONS (p in c_off's numbering, so inside the query's segment) or -1, score [Q, ksel] the
+ *   scores or +inf, where the segment has fewer than ksel candidates.  Nothing of size queries x candidates is written.
+ * agnn_smote_synth_fwd_f32:  x_over [N + S, D] = x, then the synthetic rows; y_over [N + S] likewise (optional).  The plan
+ *   (HOST, read during the call) lists the oversampled classes in output order: class i owns the class-sorted positions
+ *   t_off[i] .. t_off[i + 1] - 1, makes `copies[i]` >= 1 rows per original and writes them at s_off[i] + j copies[i] + n with label
+ *   label[i].  rows [T] maps a class-sorted position to its row of x, nbr [T, ld_nbr] is agnn_rowsel_f32's idx with
+ *   ksel >= k: rank 0 is dropped and rank 1 + choice used.  Synthetic row s = x_i + gap[s] o (x_nb - x_i), choice[s] in
+ *   [0, k - 2], gap [S, D]: both given, or both NULL and drawn from (rng, call_id) — the state is copied to rng_used for the
+ *   backward.  nb_row [S] (optional) receives the neighbour's row of x.  2 <= k < AGNN_ROWSEL_MAX_K.
+ * agnn_smote_synth_bwd_f32:  g = d x_over [N + S, D]; dx [N, D] must hold g's head on entry and receives
+ *   dx[rows[p]] += sum_n (1 - gap) o g[N + s] over the position's consecutive synthetic rows; w [S, D] = gap o g[N + s], the
+ *   addend of the neighbour's row (summed by agnn_spmm_f32 over a CSR by nb_row).  gap as in the forward, or NULL with rng_used.
+ * agnn_smote_draws_f32:  the draws of (rng, call_id) for S rows by the device functions the two kernels use.
+ * ------------------------------------------------------------------------------------------ */
+#define AGNN_ROWSEL_MAX_K  8
+#define AGNN_ROWSEL_COSINE 0
+#define AGNN_ROWSEL_SQDIST 1
+typedef struct {
+  int32_t n_seg;
+  int32_t t_off[AGNN_MAX_SEG + 1];
+  int32_t s_off[AGNN_MAX_SEG + 1];
+  int32_t copies[AGNN_MAX_SEG];
+  int64_t label[AGNN_MAX_SEG];
+} agnn_smote_plan_t;
+int agnn_rowsel_f32(const float* q, int64_t ld_q, const int32_t* q_rows, int64_t q_n, const float* c, int64_t ld_c,
+                    const int32_t* c_rows, int64_t c_n, int32_t n_seg, const int32_t* q_off, const int32_t* c_off, int32_t D,
+                    int32_t ksel, int32_t mode, int32_t* idx, float* score, agnn_stream_t stream);
+int agnn_smote_synth_fwd_f32(const float* x, int64_t ld_x, const int64_t* y, int64_t N, int32_t D, const agnn_smote_plan_t* plan,
+                             const int32_t* rows, const int32_t* nbr, int32_t ld_nbr, int32_t k, const int32_t* choice,
+                             const float* gap, const int64_t* rng, uint32_t call_id, float* x_over, int64_t ld_over,
+                             int64_t* y_over, int32_t* nb_row, int64_t* rng_used, agnn_stream_t stream);
+int agnn_smote_synth_bwd_f32(const float* g, int64_t ld_g, int64_t N, int32_t D, const agnn_smote_plan_t* plan, const int32_t* rows,
+                             const float* gap, const int64_t* rng_used, uint32_t call_id, float* dx, int64_t ld_dx, float* w,
+                             int64_t ld_w, agnn_stream_t stream);
+int agnn_smote_draws_f32(int64_t S, int32_t D, int32_t k, const int64_t* rng, uint32_t call_id, int32_t* choice, float* gap,
+                         agnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
