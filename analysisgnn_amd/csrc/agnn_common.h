@@ -31,10 +31,37 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// Workgroups of a 256-thread, one-wave-per-row launch over n_rows rows, rounded up to whole rounds over the 8 XCDs
+inline unsigned grid_for(int64_t n_rows) { return static_cast<unsigned>((((n_rows + 3) / 4) + 7) & ~int64_t{7}); }
+
 #if defined(__HIPCC__)
 // ReLU that lets a NaN through, as torch.relu does (fmaxf(NaN, 0) is 0: a poisoned row would come out of the forward pass as
 // zeros, with a finite loss, and only show as non-finite GRADIENTS — seen in round 3 when an un-normalised stack overflowed)
 __device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
+__device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+
+// MFMA vocabulary: native vectors (operands, accumulators; a staging copy of one is a register move, where a float4 struct copy
+// can become a memcpy through scratch), and the C/D layout of the 32 x 32 tile: lane l, register r -> row d_row32(r, l >> 5),
+// column l & 31
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ int d_row32(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+// XCD-aware tile order: consecutive block ids go round-robin over the 8 XCDs; ids b, b + 8, ... (one XCD) take the `tiles_n`
+// column tiles of the same row block one after the other
+__device__ __forceinline__ void xcd_tile(int b, int tiles_n, int& tile_m, int& tile_n) {
+  const int group = b / (8 * tiles_n), in_group = b - group * 8 * tiles_n;
+  tile_m = group * 8 + (in_group & 7);
+  tile_n = in_group >> 3;
+}
+// 16-byte moves of the GEMM K loops (gemm.hip, lstm.hip) ...
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+// ... and column k of a first operand [p | q] that is two matrices, never concatenated: q takes over at k = K0
+template <bool TWO>
+__device__ __forceinline__ const float* seam_at(const float* p, const float* q, int k, int K0) {
+  return TWO ? (k < K0 ? p + k : q + (k - K0)) : p + k;
+}
 
 
 // Wave-wide reductions on the DPP cross-lane paths (no LDS round trip as with __shfl_xor / ds_bpermute):
@@ -42,6 +69,10 @@ __device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
+}
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_u32(unsigned v) {
+  return static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, 0xF, 0xF, true));
 }
 __device__ __forceinline__ float lane_value(float v, int lane) {   // lane must be wave-uniform
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
@@ -65,10 +96,7 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
   return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
 }
 __device__ __forceinline__ float wave_max_dpp(float v) {
-  v = fmaxf(v, dpp_mov<0xB1>(v));
-  v = fmaxf(v, dpp_mov<0x4E>(v));
-  v = fmaxf(v, dpp_mov<0x141>(v));
-  v = fmaxf(v, dpp_mov<0x140>(v));
+  v = row16_max(v);
   return fmaxf(fmaxf(lane_value(v, 0), lane_value(v, 16)), fmaxf(lane_value(v, 32), lane_value(v, 48)));
 }
 
@@ -84,6 +112,18 @@ __device__ __forceinline__ uint4 philox(uint4 c, uint2 k) {
     k.y += 0xBB67AE85u;
   }
   return c;
+}
+// The stream itself, written once: the four words of 64-bit element index idx (tests/test_gpu_random_streams.py holds its known
+// answers).  A consumer owns only its index formula.
+__device__ __forceinline__ uint4 stream_bits(uint64_t seed, uint64_t step, uint32_t call_id, uint64_t idx) {
+  return philox(make_uint4(static_cast<uint32_t>(idx), static_cast<uint32_t>(idx >> 32), call_id, static_cast<uint32_t>(step)),
+                make_uint2(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32) ^ static_cast<uint32_t>(step >> 32)));
+}
+// Dropout at probability p drops a word below this threshold ...
+__device__ __forceinline__ uint32_t drop_threshold(float p) { return static_cast<uint32_t>(static_cast<double>(p) * 4294967296.0); }
+// ... and the factors of four words: 0 for a dropped element, `kept` (1 / (1 - p), or the caller's scale) otherwise
+__device__ __forceinline__ float4 keep_factors(uint4 r, uint32_t thr, float kept) {
+  return make_float4(r.x >= thr ? kept : 0.f, r.y >= thr ? kept : 0.f, r.z >= thr ? kept : 0.f, r.w >= thr ? kept : 0.f);
 }
 #endif
 

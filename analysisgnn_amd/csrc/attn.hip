@@ -5,12 +5,12 @@
 // All three kernels are built on v_mfma_f32_32x32x2_f32 and on one fact about it: a 32 x 32 result has its COLUMN on the lane
 // and its rows in the 16 accumulator registers (row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)), and the B operand of a following
 // product that sums over that row index is register r as it stands, when the A operand of k-step r is read at the two rows
-// crow(r, 0) / crow(r, 1) by the two lane halves.  So no score ever moves between lanes or through LDS:
+// d_row32(r, 0) / d_row32(r, 1) by the two lane halves.  So no score ever moves between lanes or through LDS:
 //
 //   forward, one wave = 32 query rows (workgroup = 2 or 4 waves = 64 / 128 rows of one head), key tiles of 32:
 //     S^T[key][query] = K Q^T            (A = K tile from LDS, B = Q in registers, pre-scaled by log2(e) / sqrt(D))
 //     online softmax per lane: a query's 32 scores are 16 registers in each of the lanes c and c + 32
-//     O^T[d][query] += V^T P^T           (A = V tile from LDS read at rows crow(r, h), B = the probabilities as they stand)
+//     O^T[d][query] += V^T P^T           (A = V tile from LDS read at rows d_row32(r, h), B = the probabilities as they stand)
 //   backward, pass 1, the same structure, one wave = 32 query rows:   dQ^T += K^T dS^T   with  S^T = K Q^T, dP^T = V dO^T
 //   backward, pass 2, mirrored, one wave = 32 KEY rows, query tiles of 32 through LDS:
 //     S = Q K^T, dP = dO V^T  (key on the lane),  dV^T += dO^T P~,  dK^T += Q^T dS
@@ -32,7 +32,8 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using agnn::f32x16;
+using agnn::d_row32;
 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
@@ -48,16 +49,10 @@ struct AttnArgs {
   uint32_t call_id;
 };
 
-__device__ __forceinline__ int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
 // keep factors (0 or 1 / (1 - p)) of keys key4 .. key4 + 3 (key4 % 4 == 0) of query row `row` = head N + query
 __device__ __forceinline__ float4 attn_keep4(uint64_t seed, uint64_t step, uint32_t call_id, uint64_t row, int64_t N, int key4, float p) {
   const uint64_t idx = row * static_cast<uint64_t>(N) + static_cast<uint32_t>(key4);
-  const uint4 r = agnn::philox(make_uint4(static_cast<uint32_t>(idx), static_cast<uint32_t>(idx >> 32), call_id, static_cast<uint32_t>(step)),
-                               make_uint2(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32) ^ static_cast<uint32_t>(step >> 32)));
-  const uint32_t thr = static_cast<uint32_t>(static_cast<double>(p) * 4294967296.0);            // drop when r < thr
-  const float inv = 1.f / (1.f - p);
-  return make_float4(r.x >= thr ? inv : 0.f, r.y >= thr ? inv : 0.f, r.z >= thr ? inv : 0.f, r.w >= thr ? inv : 0.f);
+  return agnn::keep_factors(agnn::stream_bits(seed, step, call_id, idx), agnn::drop_threshold(p), 1.f / (1.f - p));
 }
 
 template <int D>
@@ -82,8 +77,8 @@ __device__ __forceinline__ void tile_load(float4 (&sa)[Tile<D>::NLD], float4 (&s
     const int r = f / T::C4, c4 = f % T::C4;
     const int row = row0 + r;
     const bool on = f < 32 * T::C4 && row < N;
-    sa[i] = on ? *reinterpret_cast<const float4*>(A + static_cast<int64_t>(row) * ld_a + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    sb[i] = on ? *reinterpret_cast<const float4*>(B + static_cast<int64_t>(row) * ld_b + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    sa[i] = on ? *reinterpret_cast<const float4*>(A + static_cast<int64_t>(row) * ld_a + c4 * 4) : agnn::f4_zero();
+    sb[i] = on ? *reinterpret_cast<const float4*>(B + static_cast<int64_t>(row) * ld_b + c4 * 4) : agnn::f4_zero();
   }
 }
 
@@ -110,7 +105,7 @@ __device__ __forceinline__ void acc_transposed(f32x16 (&out)[Tile<D>::DT], const
   using T = Tile<D>;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const float* rowp = la + crow(r, h) * T::LD + c;
+    const float* rowp = la + d_row32(r, h) * T::LD + c;
 #pragma unroll
     for (int t = 0; t < T::DT; ++t) out[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(rowp[32 * t], x[r], out[t], 0, 0, 0);
   }
@@ -137,7 +132,7 @@ __device__ __forceinline__ void lds_clear(float* sm, int n, int tid, int nthr) {
   }
 }
 
-// multiply the 16 probabilities of the lane (query row `row`, keys key0 + crow(r, h)) by their keep factors
+// multiply the 16 probabilities of the lane (query row `row`, keys key0 + d_row32(r, h)) by their keep factors
 __device__ __forceinline__ void apply_keep_keys(f32x16& x, uint64_t seed, uint64_t step, const AttnArgs& a, uint64_t row, int key0, int h) {
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -199,7 +194,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs a, float* __restrict_
     if (key0 + 32 > N) {                           // tail keys: out of the row maximum and the sums
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (key0 + crow(r, h) >= N) s[r] = -INFINITY;
+        if (key0 + d_row32(r, h) >= N) s[r] = -INFINITY;
     }
     float mx = s[0];
 #pragma unroll
@@ -307,7 +302,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(AttnArgs a, const float* __
       dp = __builtin_amdgcn_mfma_f32_32x32x2f32(lv[c * T::LD + 2 * ks + h], g[ks], dp, 0, 0, 0);
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = (key0 + crow(r, h) < N) ? __builtin_amdgcn_exp2f(s[r]) : 0.f;
+    for (int r = 0; r < 16; ++r) s[r] = (key0 + d_row32(r, h) < N) ? __builtin_amdgcn_exp2f(s[r]) : 0.f;
     if (drop) apply_keep_keys(dp, seed, step, a, static_cast<uint64_t>(head) * N + qrow, key0, h);
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] *= dp[r] - dl;                    // dS = P o (dP o keep - delta)
@@ -386,7 +381,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv(AttnArgs a, const float* _
       tile_load<D>(sa, sb, qp, gp, a.ld, ld_do, q0 + 32, N, tid, nthr);
       row_load(q0 + 32);
     }
-    f32x16 s, dp;                                 // [query crow(r, h)][key c]
+    f32x16 s, dp;                                 // [query d_row32(r, h)][key c]
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const float4 x = srow[buf][0][2 * g + h];
@@ -405,7 +400,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv(AttnArgs a, const float* _
     if (drop) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float4 mk = attn_keep4(seed, step, a.call_id, static_cast<uint64_t>(head) * N + (q0 + crow(r, h)), N, krow & ~3, a.p);
+        const float4 mk = attn_keep4(seed, step, a.call_id, static_cast<uint64_t>(head) * N + (q0 + d_row32(r, h)), N, krow & ~3, a.p);
         const int w = krow & 3;
         const float kf = w == 0 ? mk.x : w == 1 ? mk.y : w == 2 ? mk.z : mk.w;
         pt[r] *= kf;

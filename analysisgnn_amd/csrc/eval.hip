@@ -14,10 +14,7 @@
 
 namespace {
 
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_u32(unsigned v) {
-  return static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, 0xF, 0xF, true));
-}
+using agnn::dpp_u32;
 // reductions inside a 16-lane row, as agnn::row16_max: every lane of the row ends with the result
 __device__ __forceinline__ unsigned row16_umax(unsigned v) {
   v = max(v, dpp_u32<0xB1>(v));

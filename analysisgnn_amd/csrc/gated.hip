@@ -11,7 +11,7 @@
 
 namespace {
 
-__device__ __forceinline__ float4 g4z() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+// expf (not __expf) and an IEEE divide: deliberately not the sigmoids of lstm.hip / gru.hip (they differ numerically; do not merge)
 __device__ __forceinline__ float sig(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float4 sig4(const float4& a, const float4& b, const float4& c) {
   return make_float4(sig(a.x + b.x + c.x), sig(a.y + b.y + c.y), sig(a.z + b.z + c.z), sig(a.w + b.w + c.w));
@@ -40,8 +40,8 @@ __global__ __launch_bounds__(256) void k_gated_fwd(GatedArgs g, float* __restric
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
     on[k] = (k * 256 + lane * 4) < g.H;
-    av[k] = on[k] ? ap[k * 64 + lane] : g4z();
-    acc[k] = g4z();
+    av[k] = on[k] ? ap[k * 64 + lane] : agnn::f4_zero();
+    acc[k] = agnn::f4_zero();
   }
   const int start = g.rowptr[row], end = g.rowptr[row + 1];
   for (int p = start; p < end; ++p) {
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_gated_fwd(GatedArgs g, float* __restric
     for (int k = 0; k < CH; ++k) {
       if (!on[k]) continue;
       const float4 bv = bp[k * 64 + lane], hv = hp[k * 64 + lane];
-      const float4 cv = cp ? cp[k * 64 + lane] : g4z();
+      const float4 cv = cp ? cp[k * 64 + lane] : agnn::f4_zero();
       const float4 z = sig4(av[k], bv, cv);
       acc[k].x = fmaf(z.x, hv.x, acc[k].x); acc[k].y = fmaf(z.y, hv.y, acc[k].y);
       acc[k].z = fmaf(z.z, hv.z, acc[k].z); acc[k].w = fmaf(z.w, hv.w, acc[k].w);
@@ -80,9 +80,9 @@ __global__ __launch_bounds__(256) void k_gated_bwd_dst(GatedArgs g, const float*
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
     on[k] = (k * 256 + lane * 4) < g.H;
-    av[k] = on[k] ? ap[k * 64 + lane] : g4z();
-    dv[k] = on[k] ? dp[k * 64 + lane] : g4z();
-    acc[k] = g4z();
+    av[k] = on[k] ? ap[k * 64 + lane] : agnn::f4_zero();
+    dv[k] = on[k] ? dp[k * 64 + lane] : agnn::f4_zero();
+    acc[k] = agnn::f4_zero();
   }
   const int start = g.rowptr[row], end = g.rowptr[row + 1];
   for (int p = start; p < end; ++p) {
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void k_gated_bwd_dst(GatedArgs g, const float*
     for (int k = 0; k < CH; ++k) {
       if (!on[k]) continue;
       const float4 bv = bp[k * 64 + lane], hv = hp[k * 64 + lane];
-      const float4 cv = cp ? cp[k * 64 + lane] : g4z();
+      const float4 cv = cp ? cp[k * 64 + lane] : agnn::f4_zero();
       const float4 z = sig4(av[k], bv, cv);
       const float4 t = make_float4(dv[k].x * hv.x * z.x * (1.f - z.x), dv[k].y * hv.y * z.y * (1.f - z.y),
                                    dv[k].z * hv.z * z.z * (1.f - z.z), dv[k].w * hv.w * z.w * (1.f - z.w));
@@ -125,10 +125,10 @@ __global__ __launch_bounds__(256) void k_gated_bwd_src(GatedArgs g, const float*
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
     on[k] = (k * 256 + lane * 4) < g.H;
-    bv[k] = on[k] ? bp[k * 64 + lane] : g4z();
-    hv[k] = on[k] ? hp[k * 64 + lane] : g4z();
-    accb[k] = g4z();
-    acch[k] = g4z();
+    bv[k] = on[k] ? bp[k * 64 + lane] : agnn::f4_zero();
+    hv[k] = on[k] ? hp[k * 64 + lane] : agnn::f4_zero();
+    accb[k] = agnn::f4_zero();
+    acch[k] = agnn::f4_zero();
   }
   const int start = g.rowptr[row], end = g.rowptr[row + 1];
   for (int p = start; p < end; ++p) {
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void k_gated_bwd_src(GatedArgs g, const float*
     for (int k = 0; k < CH; ++k) {
       if (!on[k]) continue;
       const float4 av = ap[k * 64 + lane], dv = dp[k * 64 + lane];
-      const float4 cv = cp ? cp[k * 64 + lane] : g4z();
+      const float4 cv = cp ? cp[k * 64 + lane] : agnn::f4_zero();
       const float4 z = sig4(av, bv[k], cv);
       acch[k].x = fmaf(z.x, dv.x, acch[k].x); acch[k].y = fmaf(z.y, dv.y, acch[k].y);
       acch[k].z = fmaf(z.z, dv.z, acch[k].z); acch[k].w = fmaf(z.w, dv.w, acch[k].w);
@@ -174,11 +174,10 @@ int gated_check(const char* who, const agnn_gated_t* g) {
 inline GatedArgs to_args(const agnn_gated_t* g) {
   return GatedArgs{g->rowptr, g->col, g->perm, g->a, g->b, g->h, g->c, g->ld, g->ld_c, static_cast<int32_t>(g->n_rows), g->H};
 }
-inline unsigned ggrid(int64_t n_rows) { return static_cast<unsigned>((((n_rows + 3) / 4) + 7) & ~int64_t{7}); }
 
 #define AGNN_GATED_LAUNCH(KERN, ...)                                                                          \
   do {                                                                                                        \
-    const dim3 grid(ggrid(g->n_rows)), block(256);                                                            \
+    const dim3 grid(agnn::grid_for(g->n_rows)), block(256);                                                            \
     hipStream_t s = static_cast<hipStream_t>(stream_);                                                        \
     if (g->H <= 256) hipLaunchKernelGGL(KERN<1>, grid, block, 0, s, to_args(g), __VA_ARGS__);                 \
     else if (g->H <= 512) hipLaunchKernelGGL(KERN<2>, grid, block, 0, s, to_args(g), __VA_ARGS__);            \

@@ -22,7 +22,10 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using agnn::f32x16;
+using agnn::f32x4;
+using agnn::ld4;
+using agnn::st4;
 
 constexpr int BM = 128, BK = 16, LDT = BK + 4;
 
@@ -55,11 +58,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) float sB[2][NN ? BK * LDN : BN * LDT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  // XCD-aware tile order: consecutive block ids go round-robin over the 8 XCDs; ids b, b + 8, ... (one XCD) take the N tiles
-  // of the same row block one after the other
-  const int b = blockIdx.x;
-  const int group = b / (8 * g.tiles_n), in_group = b - group * 8 * g.tiles_n;
-  const int tile_m = group * 8 + (in_group & 7), tile_n = in_group >> 3;
+  int tile_m, tile_n;
+  agnn::xcd_tile(blockIdx.x, g.tiles_n, tile_m, tile_n);
   const int row0 = tile_m * BM, col0 = tile_n * BN;
   if (row0 >= g.M) return;
 
@@ -69,8 +69,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
   const float* pa1 = g.a + static_cast<int64_t>(min(row0 + 64 + sr, g.M - 1)) * g.ld_a + sk;
   const float* qa0 = TWO ? g.a1 + static_cast<int64_t>(min(row0 + sr, g.M - 1)) * g.ld_a1 + sk : nullptr;
   const float* qa1 = TWO ? g.a1 + static_cast<int64_t>(min(row0 + 64 + sr, g.M - 1)) * g.ld_a1 + sk : nullptr;
-#define A0_AT(k) (TWO ? ((k) < g.K0 ? pa0 + (k) : qa0 + ((k) - g.K0)) : pa0 + (k))
-#define A1_AT(k) (TWO ? ((k) < g.K0 ? pa1 + (k) : qa1 + ((k) - g.K0)) : pa1 + (k))
+#define A0_AT(k) agnn::seam_at<TWO>(pa0, qa0, k, g.K0)
+#define A1_AT(k) agnn::seam_at<TWO>(pa1, qa1, k, g.K0)
   const int so0 = sr * LDT + sk, so1 = (64 + sr) * LDT + sk;
   // second operand: NT — rows col0 + (t / 4) (+ 64) of w[N, K], as the first; NN — k rows (t / (BN / 4)) (+ 8) of w[K, N], 16 bytes of n each
   const int nr = NN ? tid / (BN / 4) : 0, nc = NN ? 4 * (tid % (BN / 4)) : 0;
@@ -87,9 +87,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
     for (int j = 0; j < NJ; ++j) acc[i][j] = f32x16{0};
 
   const int nk = g.K / BK;
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define LD4(p) (*reinterpret_cast<const f32x4*>(p))
-#define ST4(p, v) (*reinterpret_cast<f32x4*>(p) = (v))
   // two staging register sets (X: even steps, Y: odd steps), requested TWO steps ahead; fragment sets F (kk = 0) and G (kk = 8)
   f32x4 xa0, xa1, xw0, xw1, ya0, ya1, yw0, yw1;
   f32x4 fa0, fa1, fb0, fb1, ga0, ga1, gb0, gb1;
@@ -103,23 +100,23 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
     D0 = f32x4{q_[0], q_[LDN], q_[2 * LDN], q_[3 * LDN]};                                                  \
     D1 = NJ == 2 ? f32x4{q_[32], q_[LDN + 32], q_[2 * LDN + 32], q_[3 * LDN + 32]} : D0;                   \
   } else {                                                                                                 \
-    D0 = LD4(&sB[BUF][fb + (KK)]);                                                                         \
-    D1 = NJ == 2 ? LD4(&sB[BUF][fb + 32 * LDT + (KK)]) : D0;                                               \
+    D0 = ld4(&sB[BUF][fb + (KK)]);                                                                         \
+    D1 = NJ == 2 ? ld4(&sB[BUF][fb + 32 * LDT + (KK)]) : D0;                                               \
   }
   const int last = (nk - 1) * BK;
-  xa0 = LD4(pa0); xa1 = LD4(pa1); xw0 = LD4(pw0); xw1 = LD4(pw1);
+  xa0 = ld4(pa0); xa1 = ld4(pa1); xw0 = ld4(pw0); xw1 = ld4(pw1);
   {
     const int k1 = min(BK, last);
-    ya0 = LD4(A0_AT(k1)); ya1 = LD4(A1_AT(k1)); yw0 = LD4(pw0 + k1 * wmul); yw1 = LD4(pw1 + k1 * wmul);
+    ya0 = ld4(A0_AT(k1)); ya1 = ld4(A1_AT(k1)); yw0 = ld4(pw0 + k1 * wmul); yw1 = ld4(pw1 + k1 * wmul);
   }
-  ST4(&sA[0][so0], xa0); ST4(&sA[0][so1], xa1); ST4(&sB[0][sbo0], xw0);
-  if (NJ == 2) ST4(&sB[0][sbo1], xw1);
+  st4(&sA[0][so0], xa0); st4(&sA[0][so1], xa1); st4(&sB[0][sbo0], xw0);
+  if (NJ == 2) st4(&sB[0][sbo1], xw1);
   {
     const int k2 = min(2 * BK, last);
-    xa0 = LD4(A0_AT(k2)); xa1 = LD4(A1_AT(k2)); xw0 = LD4(pw0 + k2 * wmul); xw1 = LD4(pw1 + k2 * wmul);
+    xa0 = ld4(A0_AT(k2)); xa1 = ld4(A1_AT(k2)); xw0 = ld4(pw0 + k2 * wmul); xw1 = ld4(pw1 + k2 * wmul);
   }
   __syncthreads();
-  fa0 = LD4(&sA[0][fa]); fa1 = LD4(&sA[0][fa + 32 * LDT]);
+  fa0 = ld4(&sA[0][fa]); fa1 = ld4(&sA[0][fa + 32 * LDT]);
   BFRAG(0, 0, fb0, fb1)
 
 #define MFMA_BLOCK(A0, A1, B0, B1)                                                                         \
@@ -134,21 +131,21 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
   // memory operation — a conditional load costs a full vmcnt drain at the join)
 #define STEP(CUR, KB, SA0, SA1, SW0, SW1)                                                                  \
   {                                                                                                        \
-    ga0 = LD4(&sA[CUR][fa + 8]); ga1 = LD4(&sA[CUR][fa + 32 * LDT + 8]);                                   \
+    ga0 = ld4(&sA[CUR][fa + 8]); ga1 = ld4(&sA[CUR][fa + 32 * LDT + 8]);                                   \
     BFRAG(CUR, 8, gb0, gb1)                                                                                \
     __builtin_amdgcn_sched_barrier(0);                                                                     \
     MFMA_BLOCK(fa0, fa1, fb0, fb1)                                                                         \
     __builtin_amdgcn_sched_barrier(0);                                                                     \
-    ST4(&sA[(CUR) ^ 1][so0], SA0); ST4(&sA[(CUR) ^ 1][so1], SA1); ST4(&sB[(CUR) ^ 1][sbo0], SW0);          \
-    if (NJ == 2) ST4(&sB[(CUR) ^ 1][sbo1], SW1);                                                           \
+    st4(&sA[(CUR) ^ 1][so0], SA0); st4(&sA[(CUR) ^ 1][so1], SA1); st4(&sB[(CUR) ^ 1][sbo0], SW0);          \
+    if (NJ == 2) st4(&sB[(CUR) ^ 1][sbo1], SW1);                                                           \
     {                                                                                                      \
       const int k3 = min(((KB) + 3) * BK, last);                                                           \
-      SA0 = LD4(A0_AT(k3)); SA1 = LD4(A1_AT(k3)); SW0 = LD4(pw0 + k3 * wmul); SW1 = LD4(pw1 + k3 * wmul);    \
+      SA0 = ld4(A0_AT(k3)); SA1 = ld4(A1_AT(k3)); SW0 = ld4(pw0 + k3 * wmul); SW1 = ld4(pw1 + k3 * wmul);    \
     }                                                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                                     \
     MFMA_BLOCK(ga0, ga1, gb0, gb1)                                                                         \
     __syncthreads();                                                                                       \
-    fa0 = LD4(&sA[(CUR) ^ 1][fa]); fa1 = LD4(&sA[(CUR) ^ 1][fa + 32 * LDT]);                               \
+    fa0 = ld4(&sA[(CUR) ^ 1][fa]); fa1 = ld4(&sA[(CUR) ^ 1][fa + 32 * LDT]);                               \
     BFRAG((CUR) ^ 1, 0, fb0, fb1)                                                                          \
   }
   int kb = 0;
@@ -162,8 +159,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
 #undef A1_AT
 #undef BFRAG
 #undef MFMA_BLOCK
-#undef LD4
-#undef ST4
 
   // epilogue: + bias, 128-byte row pieces (lanes 0..31 = 32 consecutive columns)
   const int cl = lane & 31, rh = 4 * (lane >> 5);
@@ -175,7 +170,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(GemmArgs g) {
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = row0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + rh;
+        const int row = row0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + rh;          // agnn::d_row32, written out: profiles/helpers_isa_identity.md
         if (row < g.M) g.c[static_cast<int64_t>(row) * g.ld_c + col] = acc[i][j][r] + bj;
       }
     }

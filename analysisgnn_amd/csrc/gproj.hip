@@ -19,7 +19,9 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using agnn::f32x16;
+using agnn::f32x4;
+using agnn::d_row32;
 
 struct GpArgs {
   const float* a;          // [n, G*K]
@@ -35,7 +37,6 @@ struct GpArgs {
   int32_t G, n_row_tiles, n_tiles32, S, rows_per_slice, sum_c;
 };
 
-__device__ __forceinline__ int d_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }   // C/D layout of 32x32 MFMA
 
 // LDS-staged forward: one workgroup = 128 rows x ONE group.  The 128 x K tile of `a` is fetched with coalesced 16-byte
 // loads (16 lanes per 256-byte row piece) and the 32 x K weight tile of each 32-class step once per workgroup (all four
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(256) void k_gproj_fwd(GpArgs p) {
       const float bias = p.b != nullptr ? p.b[off + col] : 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t ro = static_cast<int64_t>(rb) * 128 + wave * 32 + d_row(r, kk);
+        const int64_t ro = static_cast<int64_t>(rb) * 128 + wave * 32 + d_row32(r, kk);
         if (ro < p.n_rows) p.out[ro * p.ld_out + off + col] = acc[r] + bias;
       }
     }
@@ -122,7 +123,6 @@ __global__ __launch_bounds__(256) void k_gproj_fwd(GpArgs p) {
 //   * two accumulators per row tile (even / odd k-steps): the 16-step chain is issue-bound (32 cycles), not latency-bound (40).
 // D layout of the 16x16 tile: column = lane & 15 (class), rows 4q + r in register r.
 // ------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kGpMaxTiles16 = 128;      // capacity of the flat tile list (host: n_tiles32 <= 64, a 32-class tile is at most two)
 constexpr int kGpLdO = 308;             // floats per LDS row of a chunk of logits (4 * 308 = 16 mod 64 banks)
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256) void k_gproj_dx(GpArgs p) {
   for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int64_t ro = static_cast<int64_t>(rt) * 32 + d_row(r, kk);
+      const int64_t ro = static_cast<int64_t>(rt) * 32 + d_row32(r, kk);
       if (ro < p.n_rows) p.da[ro * p.ld_da + g * K + t * 32 + j] = acc[t][r];
     }
 }
@@ -429,7 +429,7 @@ __global__ __launch_bounds__(256) void k_gproj_dw(GpArgs p) {
   for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int ci = ct * 32 + d_row(r, kk);          // D row = class index (A operand), D column = k
+      const int ci = ct * 32 + d_row32(r, kk);          // D row = class index (A operand), D column = k
       if (ci < C) slab[static_cast<int64_t>(ci) * K + t * 32 + j] = acc[t][r];
     }
   if (p.slab_b != nullptr) {
@@ -520,7 +520,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     return;
   }
   // ---- zero the image once (the padding of every group stays zero)
-  for (int e = threadIdx.x * 4; e < 32 * ld_img; e += 512 * 4) *reinterpret_cast<float4*>(&sD[e]) = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int e = threadIdx.x * 4; e < 32 * ld_img; e += 512 * 4) *reinterpret_cast<float4*>(&sD[e]) = agnn::f4_zero();
   // ---- group table in lanes: lane g holds group g's class range, its 16-class steps, its place in the image
   const int gl = lane < p.G ? lane : p.G - 1;
   const int c0 = p.seg_off[gl], c1 = p.seg_off[gl + 1];
@@ -601,7 +601,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     float4 x0, x1, x2, x3, y0, y1, y2, y3, z0, z1, z2, z3;   // three weight register sets in rotation (no register moves: a
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0, acc3 = acc0;   // move would wait for the newest request)
     // the fragment of `dout` one step ahead (a class-less group's place in the image is the next group's: zero instead)
-#define GD_FRAG(D) (D.C > 0 ? *reinterpret_cast<const float4*>(&sD[(16 * D.rt + i) * ld_img + D.po + 16 * D.s + 4 * q]) : make_float4(0.f, 0.f, 0.f, 0.f))
+#define GD_FRAG(D) (D.C > 0 ? *reinterpret_cast<const float4*>(&sD[(16 * D.rt + i) * ld_img + D.po + 16 * D.s + 4 * q]) : agnn::f4_zero())
     // one step: multiply with (DC, BC); (DN, ..) is the step after it; the step after that is requested into (DF, BF), the
     // set the step before this one used
 #define GD_STEP(DC, BC, DN, DF, BF)                                                               \

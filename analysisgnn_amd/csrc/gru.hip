@@ -25,7 +25,7 @@ namespace {
 // (H = 128).  256 (H = 512) does not fit: W_hh = 768 x 256 fp32 = 768 KB against 512 KB of registers + 160 KB of LDS per CU.
 constexpr int NT = 512;        // threads per chain: 8 waves = 8 chunks of the reduction dimension
 constexpr int KC = 8;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using agnn::f32x2;
 
 // Workgroup barrier that orders LDS traffic only.  `__syncthreads()` also waits for every outstanding
 // global load/store (s_waitcnt vmcnt(0)), which would put one HBM store round trip and the prefetch of
@@ -35,6 +35,7 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // Gate non-linearities on the hardware transcendental units: v_exp_f32 and v_rcp_f32 are each good to
 // ~1 ulp, so sigmoid is ~3 ulp (3e-7 relative) — far inside the 1e-4 parity budget — at 5 instructions
 // instead of ~40 for expf + IEEE division.  This block is on the serial critical path of every step.
+// (__expf and v_rcp_f32: deliberately not lstm.hip's IEEE-divide variant nor gated.hip's expf one; they differ numerically, do not merge)
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float tanhf_(float x) { return 2.f * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * x)) - 1.f; }
 
@@ -439,7 +440,7 @@ __global__ __launch_bounds__(256) void k_gru_hprev(const float* __restrict__ y, 
     const int t = static_cast<int>(row % T);
     const bool rev = q >= Q / 2;
     const bool has = rev ? (t + 1 < T) : (t > 0);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 v = agnn::f4_zero();
     if (has) v = reinterpret_cast<const float4*>(y)[(rev ? row + 1 : row - 1) * Q + q];
     reinterpret_cast<float4*>(hp)[e] = v;
   }

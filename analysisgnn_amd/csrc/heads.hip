@@ -22,8 +22,8 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));     // staging copies as native vectors (a float4 struct copy becomes a memcpy through scratch)
+using agnn::f32x16;
+using agnn::f32x4;      // staging copies as native vectors (a float4 struct copy becomes a memcpy through scratch)
 
 constexpr int HK = 128;            // encoder output width (contraction of the first projection)
 constexpr int HJ = 64;             // hidden width of a head
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void k_heads_fwd(HeadsFwd g, int first_bloc
     // ---- + bias; accumulator layout (hidden unit = lane) -> row layout (note = lane) through the wave's own LDS tile ----
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int rl = (r & 3) + 8 * (r >> 2) + 4 * hh;
+      const int rl = agnn::d_row32(r, hh);
       sZw[rl * LDY + lr] = a0[r] + bb0;
       sZw[rl * LDY + 32 + lr] = a1[r] + bb1;
     }
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256, 2) void k_heads_fwd(HeadsFwd g, int first_bloc
         char* ot = reinterpret_cast<char*>(g.logits + c_lo + 32 * tile);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int rq = (r & 3) + 8 * (r >> 2);
+          const int rq = agnn::d_row32(r, 0);
           if (!CHECK || row0 + rq + 4 * hh < g.N) *reinterpret_cast<float*>(ot + static_cast<int64_t>(rq) * g.ld_o * 4 + vo) = (c0[r] + c1[r]) + bias;
         }
       }

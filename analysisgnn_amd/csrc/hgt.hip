@@ -28,7 +28,6 @@ struct HgtTable {
   int n_rel;
 };
 
-__device__ __forceinline__ float4 f4z() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float dot4(const float4& a, const float4& b) {
   return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w)));
 }
@@ -74,8 +73,8 @@ __device__ __forceinline__ void hgt_fwd_rows(const HgtTable& t, int r0, int r1, 
     const int f = c * 256 + lane * 4;
     on[c] = f < a.H;
     head[c] = on[c] ? f / D : 0;
-    qv[c] = on[c] ? qp[c * 64 + lane] : f4z();
-    acc[c] = f4z();
+    qv[c] = on[c] ? qp[c * 64 + lane] : agnn::f4_zero();
+    acc[c] = agnn::f4_zero();
     m[c] = -INFINITY;
     l[c] = 0.f;
   }
@@ -105,10 +104,10 @@ __device__ __forceinline__ void hgt_fwd_rows(const HgtTable& t, int r0, int r1, 
         float4 k0[CH], v0[CH], k1[CH], v1[CH];
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
-          k0[c] = on[c] ? kp0[c * 64 + lane] : f4z();
-          k1[c] = on[c] ? kp1[c * 64 + lane] : f4z();
-          v0[c] = on[c] ? vp0[c * 64 + lane] : f4z();
-          v1[c] = on[c] ? vp1[c * 64 + lane] : f4z();
+          k0[c] = on[c] ? kp0[c * 64 + lane] : agnn::f4_zero();
+          k1[c] = on[c] ? kp1[c * 64 + lane] : agnn::f4_zero();
+          v0[c] = on[c] ? vp0[c * 64 + lane] : agnn::f4_zero();
+          v1[c] = on[c] ? vp1[c * 64 + lane] : agnn::f4_zero();
         }
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
@@ -197,13 +196,13 @@ __global__ __launch_bounds__(256) void k_hgt_bwd_dst(HgtTable t, HgtArgs a, cons
     on[c] = f < a.H;
     head[c] = on[c] ? f / D : 0;
     lead[c] = on[c] && (f % D) == 0;
-    qv[c] = on[c] ? qp[c * 64 + lane] : f4z();
-    dmv[c] = on[c] ? dp[c * 64 + lane] : f4z();
-    const float4 mv = on[c] ? mp[c * 64 + lane] : f4z();
+    qv[c] = on[c] ? qp[c * 64 + lane] : agnn::f4_zero();
+    dmv[c] = on[c] ? dp[c * 64 + lane] : agnn::f4_zero();
+    const float4 mv = on[c] ? mp[c * 64 + lane] : agnn::f4_zero();
     dsum[c] = group_sum(dot4(dmv[c], mv), gl);                       // sum_e alpha_e dalpha_e = <dM, M>
     mrow[c] = m_in[static_cast<int64_t>(row) * a.heads + head[c]];
     linv[c] = linv_in[static_cast<int64_t>(row) * a.heads + head[c]];
-    dqa[c] = f4z();
+    dqa[c] = agnn::f4_zero();
   }
   // same loop structure as the forward pass: scalar index phase, column ids / COO positions of a segment in one vector
   // register each, two neighbours' K' / V' rows in flight
@@ -232,10 +231,10 @@ __global__ __launch_bounds__(256) void k_hgt_bwd_dst(HgtTable t, HgtArgs a, cons
         float4 k0[CH], v0[CH], k1[CH], v1[CH];
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
-          k0[c] = on[c] ? kp0[c * 64 + lane] : f4z();
-          k1[c] = on[c] ? kp1[c * 64 + lane] : f4z();
-          v0[c] = on[c] ? vp0[c * 64 + lane] : f4z();
-          v1[c] = on[c] ? vp1[c * 64 + lane] : f4z();
+          k0[c] = on[c] ? kp0[c * 64 + lane] : agnn::f4_zero();
+          k1[c] = on[c] ? kp1[c * 64 + lane] : agnn::f4_zero();
+          v0[c] = on[c] ? vp0[c * 64 + lane] : agnn::f4_zero();
+          v1[c] = on[c] ? vp1[c * 64 + lane] : agnn::f4_zero();
         }
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
@@ -291,8 +290,8 @@ __device__ __forceinline__ void hgt_bwd_src_rows(const int32_t* __restrict__ row
     const int f = c * 256 + lane * 4;
     on[c] = f < a.H;
     head[c] = on[c] ? f / D : 0;
-    dka[c] = f4z();
-    dva[c] = f4z();
+    dka[c] = agnn::f4_zero();
+    dva[c] = agnn::f4_zero();
   }
   const int start = ((hk_i32p)rowptr)[row];
   const int end = (rowend != nullptr) ? ((hk_i32p)rowend)[row] : ((hk_i32p)rowptr)[row + 1];
@@ -368,7 +367,6 @@ int check_shape(const char* who, int64_t n_rows, int32_t H, int32_t heads) {
   return AGNN_OK;
 }
 
-inline unsigned grid_for(int64_t n_rows) { return static_cast<unsigned>((((n_rows + 3) / 4) + 7) & ~int64_t{7}); }
 
 }  // namespace
 
@@ -390,7 +388,7 @@ extern "C" int agnn_hgt_attn_fwd_f32(int n_rel, const agnn_hgt_rel_t* rels, cons
   }
   HgtArgs a{q, ld_q, static_cast<int32_t>(n_rows), H, heads, INT32_MAX};
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  const dim3 grid(grid_for(n_rows)), block(256);
+  const dim3 grid(agnn::grid_for(n_rows)), block(256);
   if (H <= 256) hipLaunchKernelGGL(k_hgt_fwd<1>, grid, block, 0, s, t, a, out, ld_out, m_out, linv_out);
   else if (H <= 512) hipLaunchKernelGGL(k_hgt_fwd<2>, grid, block, 0, s, t, a, out, ld_out, m_out, linv_out);
   else hipLaunchKernelGGL(k_hgt_fwd<4>, grid, block, 0, s, t, a, out, ld_out, m_out, linv_out);
@@ -420,7 +418,7 @@ extern "C" int agnn_hgt_attn_fwd_multi_f32(int32_t n_items, const agnn_hgt_dst_i
     mm.a[k] = HgtArgs{it.q, it.ld_q, static_cast<int32_t>(it.n_rows), H, heads, INT32_MAX};
     mm.out[k] = it.out; mm.m_out[k] = it.m_out; mm.linv_out[k] = it.linv_out; mm.ld_out[k] = it.ld_out;
     mm.blk0[k] = blocks;
-    blocks += static_cast<int>(grid_for(it.n_rows));
+    blocks += static_cast<int>(agnn::grid_for(it.n_rows));
     ++k;
   }
   if (k == 0) return AGNN_OK;
@@ -454,7 +452,7 @@ extern "C" int agnn_hgt_attn_bwd_dst_f32(int n_rel, const agnn_hgt_rel_t* rels, 
   }
   HgtArgs a{q, ld_q, static_cast<int32_t>(n_rows), H, heads, INT32_MAX};
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  const dim3 grid(grid_for(n_rows)), block(256);
+  const dim3 grid(agnn::grid_for(n_rows)), block(256);
   if (H <= 256) hipLaunchKernelGGL(k_hgt_bwd_dst<1>, grid, block, 0, s, t, a, dm, ld_dm, out, ld_out, m_in, linv_in, dq, ld_dq);
   else if (H <= 512) hipLaunchKernelGGL(k_hgt_bwd_dst<2>, grid, block, 0, s, t, a, dm, ld_dm, out, ld_out, m_in, linv_in, dq, ld_dq);
   else hipLaunchKernelGGL(k_hgt_bwd_dst<4>, grid, block, 0, s, t, a, dm, ld_dm, out, ld_out, m_in, linv_in, dq, ld_dq);
@@ -477,7 +475,7 @@ extern "C" int agnn_hgt_attn_bwd_src_batch_f32(int32_t n_items, const agnn_hgt_s
     if (!aligned16(it.dk) || !aligned16(it.dv) || (it.ld_o & 3)) return fail(AGNN_EALIGN, "hgt_bwd_src_batch: item %d: misaligned output", i);
     b.first[b.n] = blocks;
     b.it[b.n++] = it;
-    blocks += static_cast<int>(grid_for(it.n_src_rows));
+    blocks += static_cast<int>(agnn::grid_for(it.n_src_rows));
   }
   if (b.n == 0) return AGNN_OK;
   b.first[b.n] = blocks;

@@ -29,11 +29,14 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using agnn::f32x16;
+using agnn::f32x4;
+using agnn::ld4;
+using agnn::st4;
 
 constexpr int BM = 128, BN = 128, BK = 16, LDT = BK + 4;
 
+// __expf and an IEEE divide: deliberately not gru.hip's v_rcp_f32 variant nor gated.hip's expf one (they differ numerically; do not merge)
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + __expf(-v)); }
 __device__ __forceinline__ float tanhf_(float v) { return 2.f / (1.f + __expf(-2.f * v)) - 1.f; }
 
@@ -49,10 +52,8 @@ __global__ __launch_bounds__(256, 2) void k_lstm_step(StepArgs g) {
   const agnn_lstm_step_t& it = g.it[blockIdx.y];
   const int M = static_cast<int>(it.M), K0 = it.K0, h = it.h;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware tile order (gemm.hip): ids b, b + 8, ... (one XCD) take the column tiles of one row block one after the other
-  const int b = blockIdx.x;
-  const int group = b / (8 * g.tiles_n), in_group = b - group * 8 * g.tiles_n;
-  const int tile_m = group * 8 + (in_group & 7), tile_n = in_group >> 3;
+  int tile_m, tile_n;
+  agnn::xcd_tile(blockIdx.x, g.tiles_n, tile_m, tile_n);
   const int row0 = tile_m * BM;
   if (row0 >= M) return;
 
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(256, 2) void k_lstm_step(StepArgs g) {
   const float* pw1 = it.w_ih + wr1 * K0 + sk;
   const float* qw0 = TWO ? it.w_hh + wr0 * h + sk : nullptr;
   const float* qw1 = TWO ? it.w_hh + wr1 * h + sk : nullptr;
-#define AT(p, q, k) (TWO ? ((k) < K0 ? p + (k) : q + ((k) - K0)) : p + (k))
+#define AT(p, q, k) agnn::seam_at<TWO>(p, q, k, K0)
   const int so0 = sr * LDT + sk, so1 = (64 + sr) * LDT + sk;
 
   f32x16 acc[4];
@@ -77,27 +78,25 @@ __global__ __launch_bounds__(256, 2) void k_lstm_step(StepArgs g) {
   for (int j = 0; j < 4; ++j) acc[j] = f32x16{0};
 
   const int nk = (TWO ? K0 + h : K0) / BK;
-#define LD4(p) (*reinterpret_cast<const f32x4*>(p))
-#define ST4(p, v) (*reinterpret_cast<f32x4*>(p) = (v))
   // two staging register sets (X: even steps, Y: odd steps), requested TWO steps ahead; fragment sets F (kk = 0) and G (kk = 8)
   f32x4 xa0, xa1, xw0, xw1, ya0, ya1, yw0, yw1;
   f32x4 fa, fb0, fb1, fb2, fb3, ga, gb0, gb1, gb2, gb3;
   const int fr = lane & 31, fk = 4 * (lane >> 5);
   const int foa = (32 * wave + fr) * LDT + fk, fob = fr * LDT + fk;
 #define FRAGS(BUF, KK, A, B0, B1, B2, B3)                                                                  \
-  A = LD4(&sA[BUF][foa + (KK)]);                                                                           \
-  B0 = LD4(&sB[BUF][fob + (KK)]); B1 = LD4(&sB[BUF][fob + 32 * LDT + (KK)]);                               \
-  B2 = LD4(&sB[BUF][fob + 64 * LDT + (KK)]); B3 = LD4(&sB[BUF][fob + 96 * LDT + (KK)]);
+  A = ld4(&sA[BUF][foa + (KK)]);                                                                           \
+  B0 = ld4(&sB[BUF][fob + (KK)]); B1 = ld4(&sB[BUF][fob + 32 * LDT + (KK)]);                               \
+  B2 = ld4(&sB[BUF][fob + 64 * LDT + (KK)]); B3 = ld4(&sB[BUF][fob + 96 * LDT + (KK)]);
   const int last = (nk - 1) * BK;
-  xa0 = LD4(pa0); xa1 = LD4(pa1); xw0 = LD4(pw0); xw1 = LD4(pw1);
+  xa0 = ld4(pa0); xa1 = ld4(pa1); xw0 = ld4(pw0); xw1 = ld4(pw1);
   {
     const int k1 = min(BK, last);
-    ya0 = LD4(AT(pa0, qa0, k1)); ya1 = LD4(AT(pa1, qa1, k1)); yw0 = LD4(AT(pw0, qw0, k1)); yw1 = LD4(AT(pw1, qw1, k1));
+    ya0 = ld4(AT(pa0, qa0, k1)); ya1 = ld4(AT(pa1, qa1, k1)); yw0 = ld4(AT(pw0, qw0, k1)); yw1 = ld4(AT(pw1, qw1, k1));
   }
-  ST4(&sA[0][so0], xa0); ST4(&sA[0][so1], xa1); ST4(&sB[0][so0], xw0); ST4(&sB[0][so1], xw1);
+  st4(&sA[0][so0], xa0); st4(&sA[0][so1], xa1); st4(&sB[0][so0], xw0); st4(&sB[0][so1], xw1);
   {
     const int k2 = min(2 * BK, last);
-    xa0 = LD4(AT(pa0, qa0, k2)); xa1 = LD4(AT(pa1, qa1, k2)); xw0 = LD4(AT(pw0, qw0, k2)); xw1 = LD4(AT(pw1, qw1, k2));
+    xa0 = ld4(AT(pa0, qa0, k2)); xa1 = ld4(AT(pa1, qa1, k2)); xw0 = ld4(AT(pw0, qw0, k2)); xw1 = ld4(AT(pw1, qw1, k2));
   }
   __syncthreads();
   FRAGS(0, 0, fa, fb0, fb1, fb2, fb3)
@@ -117,12 +116,12 @@ __global__ __launch_bounds__(256, 2) void k_lstm_step(StepArgs g) {
     __builtin_amdgcn_sched_barrier(0);                                                                     \
     MFMA_BLOCK(fa, fb0, fb1, fb2, fb3)                                                                     \
     __builtin_amdgcn_sched_barrier(0);                                                                     \
-    ST4(&sA[(CUR) ^ 1][so0], SA0); ST4(&sA[(CUR) ^ 1][so1], SA1);                                          \
-    ST4(&sB[(CUR) ^ 1][so0], SW0); ST4(&sB[(CUR) ^ 1][so1], SW1);                                          \
+    st4(&sA[(CUR) ^ 1][so0], SA0); st4(&sA[(CUR) ^ 1][so1], SA1);                                          \
+    st4(&sB[(CUR) ^ 1][so0], SW0); st4(&sB[(CUR) ^ 1][so1], SW1);                                          \
     {                                                                                                      \
       const int k3 = min(((KB) + 3) * BK, last);                                                           \
-      SA0 = LD4(AT(pa0, qa0, k3)); SA1 = LD4(AT(pa1, qa1, k3));                                            \
-      SW0 = LD4(AT(pw0, qw0, k3)); SW1 = LD4(AT(pw1, qw1, k3));                                            \
+      SA0 = ld4(AT(pa0, qa0, k3)); SA1 = ld4(AT(pa1, qa1, k3));                                            \
+      SW0 = ld4(AT(pw0, qw0, k3)); SW1 = ld4(AT(pw1, qw1, k3));                                            \
     }                                                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                                     \
     MFMA_BLOCK(ga, gb0, gb1, gb2, gb3)                                                                     \
@@ -139,8 +138,6 @@ __global__ __launch_bounds__(256, 2) void k_lstm_step(StepArgs g) {
 #undef MFMA_BLOCK
 #undef FRAGS
 #undef AT
-#undef LD4
-#undef ST4
 
   // epilogue: the cell on the four gates of (row, unit) that this lane holds; 128-byte row pieces (lanes 0..31 = 32 units)
   const int u = 32 * tile_n + (lane & 31), rh = 4 * (lane >> 5);
@@ -150,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void k_lstm_step(StepArgs g) {
   const int64_t ld_act = 4 * static_cast<int64_t>(h);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = row0 + 32 * wave + (r & 3) + 8 * (r >> 2) + rh;
+    const int row = row0 + 32 * wave + agnn::d_row32(r, 0) + rh;
     const bool live = row < M;
     const int64_t rc = min(row, M - 1);
     const float gi = sigmoidf_(acc[0][r] + bi), gf = sigmoidf_(acc[1][r] + bf);

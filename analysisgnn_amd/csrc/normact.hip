@@ -31,16 +31,11 @@ struct NaArgs {
   int32_t seg;             // statistics over segments of `seg` floats of the row (seg == H: plain LayerNorm)
 };
 
-using agnn::philox;   // agnn_common.h
-
 template <class Args>
 __device__ __forceinline__ float4 keep_mask(const Args& a, int64_t row, int chunk_lane, float scale) {
   const uint64_t seed = static_cast<uint64_t>(a.rng[0]), step = static_cast<uint64_t>(a.rng[1]);
   const uint64_t idx = static_cast<uint64_t>(row) * 256u + static_cast<uint32_t>(chunk_lane);     // one counter per float4
-  const uint4 r = philox(make_uint4(static_cast<uint32_t>(idx), static_cast<uint32_t>(idx >> 32), a.call_id, static_cast<uint32_t>(step)),
-                         make_uint2(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32) ^ static_cast<uint32_t>(step >> 32)));
-  const uint32_t thr = static_cast<uint32_t>(static_cast<double>(a.p) * 4294967296.0);            // drop when r < thr
-  return make_float4(r.x >= thr ? scale : 0.f, r.y >= thr ? scale : 0.f, r.z >= thr ? scale : 0.f, r.w >= thr ? scale : 0.f);
+  return agnn::keep_factors(agnn::stream_bits(seed, step, a.call_id, idx), agnn::drop_threshold(a.p), scale);
 }
 
 __device__ __forceinline__ float wsum(float v) { return agnn::wave_sum_dpp(v); }
@@ -74,7 +69,7 @@ __global__ __launch_bounds__(256) void k_na_fwd(NaArgs a, float* __restrict__ y,
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     on[c] = (c * 256 + lane * 4) < a.H;
-    v[c] = on[c] ? xp[c * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+    v[c] = on[c] ? xp[c * 64 + lane] : agnn::f4_zero();
     if (pre) { v[c].x = agnn::relu_nan(v[c].x); v[c].y = agnn::relu_nan(v[c].y); v[c].z = agnn::relu_nan(v[c].z); v[c].w = agnn::relu_nan(v[c].w); }
     s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
   }
@@ -151,10 +146,10 @@ __global__ __launch_bounds__(256) void k_na_bwd(NaArgs a, const float* __restric
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     on[c] = (cb + c * 256 + lane * 4) < a.H;
-    gm[c] = on[c] ? reinterpret_cast<const float4*>(a.gamma + cb)[c * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
-    bt[c] = on[c] ? reinterpret_cast<const float4*>(a.beta + cb)[c * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
-    dg[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    db[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    gm[c] = on[c] ? reinterpret_cast<const float4*>(a.gamma + cb)[c * 64 + lane] : agnn::f4_zero();
+    bt[c] = on[c] ? reinterpret_cast<const float4*>(a.beta + cb)[c * 64 + lane] : agnn::f4_zero();
+    dg[c] = agnn::f4_zero();
+    db[c] = agnn::f4_zero();
   }
   for (int64_t row = wave_g; row < a.n; row += n_waves) {
     const float4* xp = reinterpret_cast<const float4*>(a.x + row * a.ld_x + cb);
@@ -167,12 +162,12 @@ __global__ __launch_bounds__(256) void k_na_bwd(NaArgs a, const float* __restric
       const int sidx = whole ? 0 : (on[c] ? (cb + c * 256 + lane * 4) / a.seg : 0);
       const float mean = mean_in[row * nseg + sidx], rstd = rstd_in[row * nseg + sidx];
       rs[c] = rstd;
-      xr[c] = on[c] ? xp[c * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
-      float4 g = on[c] ? gp[c * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+      xr[c] = on[c] ? xp[c * 64 + lane] : agnn::f4_zero();
+      float4 g = on[c] ? gp[c * 64 + lane] : agnn::f4_zero();
       float4 v = xr[c];
       if (pre) { v.x = agnn::relu_nan(v.x); v.y = agnn::relu_nan(v.y); v.z = agnn::relu_nan(v.z); v.w = agnn::relu_nan(v.w); }
       xh[c] = make_float4((v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd);
-      if (!on[c]) xh[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (!on[c]) xh[c] = agnn::f4_zero();
       if (drop) {
         const float4 m = keep_mask(a, row, cb / 4 + c * 64 + lane, scale);
         g.x *= m.x; g.y *= m.y; g.z *= m.z; g.w *= m.w;
@@ -354,7 +349,7 @@ __global__ __launch_bounds__(256) void k_mix_bwd(MixArgs a, const float* __restr
     for (int c = 0; c < CH; ++c) {
       if ((c * 256 + lane * 4) >= a.H) continue;
       const float4 ov = op[c * 64 + lane];
-      const float4 xv = xp != nullptr ? xp[c * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 xv = xp != nullptr ? xp[c * 64 + lane] : agnn::f4_zero();
       float4 g = gp[c * 64 + lane];
       const float4 d = make_float4(ov.x - xv.x, ov.y - xv.y, ov.z - xv.z, ov.w - xv.w);
       if (drop) {

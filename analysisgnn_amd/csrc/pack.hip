@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) void k_pack(PackTable t) {
       if (e >= (total >> 2)) break;
       const int64_t r = static_cast<uint32_t>(e) / static_cast<uint32_t>(c4);       // 32-bit: an item has < 2^31 elements (host-checked)
       const int c = static_cast<int>(e - r * c4) * 4;
-      float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 s = agnn::f4_zero();
       if (it.n_src > 0) s = *reinterpret_cast<const float4*>(it.src[0] + r * it.ld_src + c);
       for (int k = 1; k < it.n_src; ++k) {
         const float4 v = *reinterpret_cast<const float4*>(it.src[k] + r * it.ld_src + c);
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void k_gather(GatherTable t) {
     const int64_t e = (static_cast<int64_t>(base) + u * 256 + threadIdx.x) * 4;
     if (e >= n) break;
     if (vec && e + 3 < n) {
-      *reinterpret_cast<float4*>(dst + e) = src ? *reinterpret_cast<const float4*>(src + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(dst + e) = src ? *reinterpret_cast<const float4*>(src + e) : agnn::f4_zero();
     } else {
       for (int k = 0; k < 4 && e + k < n; ++k) dst[e + k] = src ? src[e + k] : 0.f;
     }

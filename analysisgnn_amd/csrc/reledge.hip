@@ -14,7 +14,6 @@
 
 namespace {
 
-__device__ __forceinline__ float4 r4z() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }     // torch.abs' subgradient: sign(0) = 0
 
 struct AbsDiffArgs {
@@ -37,9 +36,9 @@ __global__ __launch_bounds__(256) void k_absdiff_fwd(AbsDiffArgs g, float* __res
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
     on[k] = (k * 256 + lane * 4) < g.H;
-    hv[k] = on[k] ? hp[k * 64 + lane] : r4z();
-    as[k] = r4z();
-    ad[k] = r4z();
+    hv[k] = on[k] ? hp[k * 64 + lane] : agnn::f4_zero();
+    as[k] = agnn::f4_zero();
+    ad[k] = agnn::f4_zero();
   }
   const int start = g.rowptr[row], end = g.rowptr[row + 1];
   for (int p = start; p < end; ++p) {
@@ -76,9 +75,9 @@ __global__ __launch_bounds__(256) void k_absdiff_bwd(AbsDiffArgs g, const float*
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
     on[k] = (k * 256 + lane * 4) < g.H;
-    hv[k] = on[k] ? hp[k * 64 + lane] : r4z();
-    gv[k] = (!BY_COL && on[k] && gp != nullptr) ? gp[k * 64 + lane] : r4z();
-    acc[k] = r4z();
+    hv[k] = on[k] ? hp[k * 64 + lane] : agnn::f4_zero();
+    gv[k] = (!BY_COL && on[k] && gp != nullptr) ? gp[k * 64 + lane] : agnn::f4_zero();
+    acc[k] = agnn::f4_zero();
   }
   const int start = g.rowptr[row], end = g.rowptr[row + 1];
   for (int p = start; p < end; ++p) {
@@ -90,7 +89,7 @@ __global__ __launch_bounds__(256) void k_absdiff_bwd(AbsDiffArgs g, const float*
     for (int k = 0; k < CH; ++k) {
       if (!on[k]) continue;
       const float4 v = np[k * 64 + lane];
-      float4 w = BY_COL ? (gdp ? gdp[k * 64 + lane] : r4z()) : gv[k];
+      float4 w = BY_COL ? (gdp ? gdp[k * 64 + lane] : agnn::f4_zero()) : gv[k];
       acc[k].x = fmaf(sgn(hv[k].x - v.x), w.x, acc[k].x); acc[k].y = fmaf(sgn(hv[k].y - v.y), w.y, acc[k].y);
       acc[k].z = fmaf(sgn(hv[k].z - v.z), w.z, acc[k].z); acc[k].w = fmaf(sgn(hv[k].w - v.w), w.w, acc[k].w);
       if (gsp) {
@@ -122,7 +121,6 @@ int ad_check(const char* who, const int32_t* rowptr, const int32_t* col, const f
   return 0;
 }
 
-inline unsigned ad_grid(int64_t n_rows) { return static_cast<unsigned>((((n_rows + 3) / 4) + 7) & ~int64_t{7}); }
 
 }  // namespace
 
@@ -133,7 +131,7 @@ extern "C" int agnn_absdiff_fwd_f32(const int32_t* rowptr, const int32_t* col, c
   if (!out_s && !out_d) return fail(AGNN_EINVAL, "absdiff_fwd: no output requested");
   if ((out_s && !aligned16(out_s)) || (out_d && !aligned16(out_d)) || (ld_out & 3) || ld_out < H) return fail(AGNN_EALIGN, "absdiff_fwd: outputs misaligned or ld_out < H");
   const AbsDiffArgs g{rowptr, col, h, ld, static_cast<int32_t>(n_rows), H};
-  const dim3 grid(ad_grid(n_rows)), block(256);
+  const dim3 grid(agnn::grid_for(n_rows)), block(256);
   hipStream_t s = static_cast<hipStream_t>(stream_);
   if (H <= 256) hipLaunchKernelGGL(k_absdiff_fwd<1>, grid, block, 0, s, g, out_s, out_d, ld_out);
   else if (H <= 512) hipLaunchKernelGGL(k_absdiff_fwd<2>, grid, block, 0, s, g, out_s, out_d, ld_out);
@@ -151,7 +149,7 @@ extern "C" int agnn_absdiff_bwd_f32(const int32_t* rowptr, const int32_t* col, c
   if ((gd && !aligned16(gd)) || (gs && !aligned16(gs)) || (ld_g & 3) || ld_g < H) return fail(AGNN_EALIGN, "absdiff_bwd: gradients misaligned or ld_g < H");
   if (gs && !by_col) return fail(AGNN_EINVAL, "absdiff_bwd: the sum term's gradient flows to the gathered end only (by_col = 1)");
   const AbsDiffArgs g{rowptr, col, h, ld, static_cast<int32_t>(n_rows), H};
-  const dim3 grid(ad_grid(n_rows)), block(256);
+  const dim3 grid(agnn::grid_for(n_rows)), block(256);
   hipStream_t s = static_cast<hipStream_t>(stream_);
 #define AD_LAUNCH(CH)                                                                                              \
   do {                                                                                                             \

@@ -48,8 +48,8 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using agnn::f32x16;
+using agnn::f32x4;
 
 constexpr int kD = 64;
 
@@ -75,7 +75,7 @@ struct ReltArgs {
 
 // C/D layout of both MFMAs (T = 32: v_mfma_f32_32x32x2_f32, 16 registers; T = 16: v_mfma_f32_16x16x4_f32, 4 registers):
 // lane l, register q -> row (q&3) + 4*(64/T)*(q>>2) + 4*(l/T), column l % T.  `kk` = l / T; `base` (a first row, or 0) is added
-// in its own type, first.
+// in its own type, first.  (T = 32 without a base is agnn::d_row32; this one stays: profiles/relt_isa_identity.md.)
 template <int T, class B>
 __device__ __forceinline__ constexpr B cd_row(B base, int q, int kk) { return base + (q & 3) + 4 * (64 / T) * (q >> 2) + 4 * kk; }
 
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void k_relt(ReltArgs p) {
   if (rowc > p.n_rows - 1) rowc = p.n_rows - 1;
 
   // the shared stages (above), bound to this kernel's operands
-  float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = w0, w2 = w0, w3 = w0;    // the next relation's weights
+  float4 w0 = agnn::f4_zero(), w1 = w0, w2 = w0, w3 = w0;    // the next relation's weights
   auto fetch = [&](int r) { fetch_w(reinterpret_cast<const float4*>(I.w + static_cast<size_t>(r * p.heads + h) * D * D) + tid, 256, w0, w1, w2, w3); };
   auto put = [&](int buf) { put_w(sW[buf], tid, w0, w1, w2, w3); };
   const float* xrow = I.x + rowc * I.ld_x + kk * 32;
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(256) void k_relt_wide(ReltArgs p) {
   int64_t rowc = row0 + c32;
   if (rowc > p.n_rows - 1) rowc = p.n_rows - 1;
 
-  float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = w0, w2 = w0, w3 = w0;
+  float4 w0 = agnn::f4_zero(), w1 = w0, w2 = w0, w3 = w0;
   const float* const wsrc = I.w + (tid >> 4) * D + ct * 64 + (tid & 15) * 4;      // this thread's 16 bytes of rows tid/16 + 16 j
   auto fetch = [&](int r, int kc) {
     fetch_w(reinterpret_cast<const float4*>(wsrc + (static_cast<size_t>(r * p.heads + h) * D + kc * 64) * D), 4 * D, w0, w1, w2, w3);

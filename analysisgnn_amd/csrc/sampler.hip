@@ -39,21 +39,8 @@ struct SamplerArgs {
   agnn_sampler_t c;
 };
 
-__device__ __forceinline__ uint32_t s_mulhi(uint32_t a, uint32_t b) { return __umulhi(a, b); }
-
-__device__ __forceinline__ uint4 s_philox(uint4 c, uint2 k) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = s_mulhi(0xD2511F53u, c.x), l0 = 0xD2511F53u * c.x;
-    const uint32_t h1 = s_mulhi(0xCD9E8D57u, c.z), l1 = 0xCD9E8D57u * c.z;
-    c = make_uint4(h1 ^ c.y ^ k.x, l1, h0 ^ c.w ^ k.y, l0);
-    k.x += 0x9E3779B9u;
-    k.y += 0xBB67AE85u;
-  }
-  return c;
-}
-
 // Positions (into the in-neighbour list of length deg) of the sampled neighbours, ascending; returns how many.
+// The sampler's own Philox contract, NOT agnn::stream_bits: key = (seed lo, seed hi), counter = (dst, tag, t >> 2, step); keep it apart.
 __device__ __forceinline__ int select_positions(int deg, int fan, uint32_t dst, uint32_t tag, uint32_t step, uint2 key, int* pos) {
   if (deg <= fan) {
     for (int k = 0; k < deg; ++k) pos[k] = k;
@@ -62,10 +49,10 @@ __device__ __forceinline__ int select_positions(int deg, int fan, uint32_t dst, 
   int m = 0;
   uint4 rnd = make_uint4(0, 0, 0, 0);
   for (int t = 0; t < deg && m < fan; ++t) {
-    if ((t & 3) == 0) rnd = s_philox(make_uint4(dst, tag, static_cast<uint32_t>(t >> 2), step), key);
+    if ((t & 3) == 0) rnd = agnn::philox(make_uint4(dst, tag, static_cast<uint32_t>(t >> 2), step), key);
     const uint32_t u = (t & 3) == 0 ? rnd.x : (t & 3) == 1 ? rnd.y : (t & 3) == 2 ? rnd.z : rnd.w;
     // select with probability (fan - m) / (deg - t)
-    if (s_mulhi(u, static_cast<uint32_t>(deg - t)) < static_cast<uint32_t>(fan - m)) pos[m++] = t;
+    if (__umulhi(u, static_cast<uint32_t>(deg - t)) < static_cast<uint32_t>(fan - m)) pos[m++] = t;
   }
   return m;
 }
@@ -388,7 +375,7 @@ __global__ __launch_bounds__(256) void k_gather_rows(const float* __restrict__ s
     const int64_t i = e / H4;
     const int c4 = static_cast<int>(e - i * H4);
     const int g = gid[i];
-    const float4 v = g >= 0 ? *reinterpret_cast<const float4*>(src + static_cast<int64_t>(g) * ld_src + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 v = g >= 0 ? *reinterpret_cast<const float4*>(src + static_cast<int64_t>(g) * ld_src + 4 * c4) : agnn::f4_zero();
     *reinterpret_cast<float4*>(out + i * ld_out + 4 * c4) = v;
   }
 }

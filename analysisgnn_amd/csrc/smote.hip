@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void k_rowsel(const float* __restrict__ q, int
 
   for (int e = tid; e < kRsQ * D4; e += 256) {
     const int r = e / D4, f = e - r * D4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 v = agnn::f4_zero();
     if (q0 + r < q1) {
       const int64_t row = q_rows ? q_rows[q0 + r] : q0 + r;
       v = (row >= 0 && row < q_n) ? *reinterpret_cast<const float4*>(q + row * ld_q + 4 * f) : make_float4(nanv, nanv, nanv, nanv);
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void k_rowsel(const float* __restrict__ q, int
   const int ql = tid & (kRsQ - 1), slice = tid >> 4;
   float qq = 0.f;
   if (MODE == 0) {
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 a = agnn::f4_zero();
     for (int f = 0; f < D4; ++f) {
       const float4 v = q_s[ql * qs4 + f];
       a.x = fmaf(v.x, v.x, a.x); a.y = fmaf(v.y, v.y, a.y); a.z = fmaf(v.z, v.z, a.z); a.w = fmaf(v.w, v.w, a.w);
@@ -103,13 +103,13 @@ __global__ __launch_bounds__(256) void k_rowsel(const float* __restrict__ q, int
   for (int c0 = cb; c0 < ce; c0 += kRsTile) {
     float4 acc[4], nrm[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) { acc[u] = make_float4(0.f, 0.f, 0.f, 0.f); nrm[u] = make_float4(0.f, 0.f, 0.f, 0.f); }
+    for (int u = 0; u < 4; ++u) { acc[u] = agnn::f4_zero(); nrm[u] = agnn::f4_zero(); }
     for (int d0 = 0; d0 < D4; d0 += kRsDc / 4) {
       const int w4 = min(kRsDc / 4, D4 - d0);
       __syncthreads();
       for (int e = tid; e < kRsTile * w4; e += 256) {
         const int r = e / w4, f = e - r * w4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 v = agnn::f4_zero();
         if (c0 + r < ce) {
           const int64_t row = c_rows ? c_rows[c0 + r] : c0 + r;
           v = (row >= 0 && row < c_n) ? *reinterpret_cast<const float4*>(c + row * ld_c + 4 * (d0 + f)) : make_float4(nanv, nanv, nanv, nanv);
@@ -171,19 +171,15 @@ __global__ __launch_bounds__(256) void k_rowsel(const float* __restrict__ q, int
 }
 
 // ---- draws ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 smote_bits(uint64_t seed, uint64_t step, uint32_t call_id, uint64_t e) {
-  return agnn::philox(make_uint4(static_cast<uint32_t>(e), static_cast<uint32_t>(e >> 32), call_id, static_cast<uint32_t>(step)),
-                      make_uint2(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32) ^ static_cast<uint32_t>(step >> 32)));
-}
 // gap of columns 4 d4 .. 4 d4 + 3 of synthetic row s: uniform on [0, 1) in steps of 2^-24
 __device__ __forceinline__ float4 smote_gap4(uint64_t seed, uint64_t step, uint32_t call_id, int64_t s, int D4, int d4) {
-  const uint4 r = smote_bits(seed, step, call_id, static_cast<uint64_t>(s) * static_cast<uint64_t>(D4) + static_cast<uint64_t>(d4));
+  const uint4 r = agnn::stream_bits(seed, step, call_id, static_cast<uint64_t>(s) * static_cast<uint64_t>(D4) + static_cast<uint64_t>(d4));
   const float sc = 1.f / 16777216.f;
   return make_float4((r.x >> 8) * sc, (r.y >> 8) * sc, (r.z >> 8) * sc, (r.w >> 8) * sc);
 }
 // neighbour choice of synthetic row s: uniform on 0 .. k - 2 (torch.randint(0, k - 1): the k-th neighbour is never used)
 __device__ __forceinline__ int smote_choice(uint64_t seed, uint64_t step, uint32_t call_id, int64_t s, int k) {
-  const uint4 r = smote_bits(seed, step, call_id, (1ull << 62) + static_cast<uint64_t>(s));
+  const uint4 r = agnn::stream_bits(seed, step, call_id, (1ull << 62) + static_cast<uint64_t>(s));
   return static_cast<int>(__umulhi(r.x, static_cast<uint32_t>(k - 1)));
 }
 
@@ -273,7 +269,7 @@ __global__ __launch_bounds__(256) void k_smote_bwd(const float* __restrict__ g, 
   const int64_t s0 = plan.s_off[seg] + static_cast<int64_t>(pos - plan.t_off[seg]) * copies;
   uint64_t seed = 0, step = 0;
   if (gap == nullptr) { seed = static_cast<uint64_t>(rng_used[0]); step = static_cast<uint64_t>(rng_used[1]); }
-  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 a = agnn::f4_zero();
   for (int n = 0; n < copies; ++n) {
     const int64_t s = s0 + n;
     const float4 gs = *reinterpret_cast<const float4*>(g + (N + s) * ld_g + 4 * d4);

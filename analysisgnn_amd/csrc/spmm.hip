@@ -47,7 +47,7 @@ struct SpmmArgs {
   const float* self2_scale;
 };
 
-__device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+using agnn::f4_zero;
 __device__ __forceinline__ void f4_fma(float4& a, float w, const float4& v) {
   a.x = fmaf(w, v.x, a.x);
   a.y = fmaf(w, v.y, a.y);

@@ -44,11 +44,7 @@ struct TaskAttnArgs {
 __device__ __forceinline__ float4 task_keep4(uint64_t seed, uint64_t step, uint32_t call_id, int64_t n, int heads, int h, int i, int g, float p) {
   const uint64_t idx = ((static_cast<uint64_t>(n) * static_cast<uint32_t>(heads) + static_cast<uint32_t>(h)) * 32u + static_cast<uint32_t>(i)) * 32u +
                        static_cast<uint32_t>(4 * g);
-  const uint4 r = agnn::philox(make_uint4(static_cast<uint32_t>(idx), static_cast<uint32_t>(idx >> 32), call_id, static_cast<uint32_t>(step)),
-                               make_uint2(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32) ^ static_cast<uint32_t>(step >> 32)));
-  const uint32_t thr = static_cast<uint32_t>(static_cast<double>(p) * 4294967296.0);            // drop when r < thr
-  const float inv = 1.f / (1.f - p);
-  return make_float4(r.x >= thr ? inv : 0.f, r.y >= thr ? inv : 0.f, r.z >= thr ? inv : 0.f, r.w >= thr ? inv : 0.f);
+  return agnn::keep_factors(agnn::stream_bits(seed, step, call_id, idx), agnn::drop_threshold(p), 1.f / (1.f - p));
 }
 
 // `rows` rows of nc4 float4 from src (row stride ld) to LDS rows of ldr floats, at column col0

@@ -16,7 +16,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using agnn::f32x16;
 
 struct WgArgs {
   const float* dy;
@@ -147,7 +147,7 @@ __device__ __forceinline__ void wgrad_tile(const WgArgs& a, const int tile, cons
   const int ob = to * 128 + wm * 64, ib = ti * 128 + wn * 64;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int i = (r & 3) + 8 * (r >> 2) + 4 * kk;
+    const int i = agnn::d_row32(r, kk);
     float* row0 = slab + static_cast<int64_t>(ob + 2 * i) * a.in_pad + ib + 2 * c32;          // output feature ob+2i   (tile c = 0)
     float* row1 = row0 + a.in_pad;                                                            // output feature ob+2i+1 (tile c = 1)
     *reinterpret_cast<float2*>(row0) = make_float2(acc00[r], acc01[r]);

@@ -19,7 +19,7 @@ M32 = 0xFFFFFFFF
 
 
 def philox4x32_10(c: Sequence[int], k: Sequence[int]) -> Tuple[int, int, int, int]:
-    """Philox-4x32-10 (Salmon et al. 2011), the same round function as csrc/sampler.hip / normact.hip."""
+    """Philox-4x32-10 (Salmon et al. 2011), the same round function as agnn::philox in csrc/agnn_common.h."""
     c0, c1, c2, c3 = (int(v) & M32 for v in c)
     k0, k1 = (int(v) & M32 for v in k)
     for _ in range(10):
