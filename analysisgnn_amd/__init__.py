@@ -6,3 +6,14 @@ that mirrors the reference's encoder / operator interface.  There is no CPU fall
 compute entry point raises if the HIP library or a GPU is missing.
 """
 __version__ = "0.1.0"
+
+_PRETRAIN = ("PreEncoder", "pretrain_objective", "PretrainMetrics", "LinkPlan", "link_plan", "link_plans", "link_bce", "link_candidates")
+
+
+def __getattr__(name):
+    """The pretraining stage's public names (analysisgnn_amd/pretrain.py), resolved on first use: importing the package stays
+    as light as before."""
+    if name in _PRETRAIN:
+        from . import pretrain
+        return getattr(pretrain, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -152,6 +152,18 @@ class SmotePlan(C.Structure):
                 ("copies", C.c_int32 * MAX_SEG), ("label", C.c_int64 * MAX_SEG)]
 
 
+class LinkTask(C.Structure):
+    _fields_ = [("z", C.c_void_p), ("ld_z", C.c_int64), ("n", C.c_int64), ("src", C.c_void_p), ("dst", C.c_void_p), ("E", C.c_int64),
+                ("limit", C.c_int64), ("t_rowptr", C.c_void_p), ("t_col", C.c_void_p), ("logit", C.c_void_p), ("label", C.c_void_p),
+                ("g", C.c_void_p), ("loss", C.c_void_p), ("inv_cnt", C.c_void_p), ("counts", C.c_void_p)]
+
+
+class LinkBwd(C.Structure):
+    _fields_ = [("z", C.c_void_p), ("ld_z", C.c_int64), ("n", C.c_int64), ("g", C.c_void_p), ("E", C.c_int64), ("s_rowptr", C.c_void_p),
+                ("s_col", C.c_void_p), ("s_perm", C.c_void_p), ("d_rowptr", C.c_void_p), ("d_col", C.c_void_p), ("d_perm", C.c_void_p),
+                ("dz", C.c_void_p), ("ld_dz", C.c_int64)]
+
+
 _lib: Optional[C.CDLL] = None
 
 # every exported symbol of include/agnn.h: (name, restype, argtypes)
@@ -322,6 +334,9 @@ SIGNATURES = {
     "agnn_smote_synth_bwd_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(SmotePlan), C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "agnn_smote_draws_f32": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "agnn_link_bce_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(LinkTask)]),
+    "agnn_link_bce_fwd_f32": (C.c_int, [C.c_int32, C.POINTER(LinkTask), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "agnn_link_bce_bwd_f32": (C.c_int, [C.c_int32, C.POINTER(LinkBwd), C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 

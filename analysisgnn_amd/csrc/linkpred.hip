@@ -1,0 +1,373 @@
+// Link prediction of the pretraining stage (ref: models/analysis.py:360-406 `PreEncoder`, :697-744 `PreEncoderPL._common_step`):
+// every candidate edge e = (s, d) of a task is scored by the dot product <z[s], z[d]> and trained with BCEWithLogitsLoss against
+// its membership in the task's true relation.  The reference gathers both endpoint rows into [E, H] matrices, multiplies, sums,
+// compacts candidates and true edges to the batch by boolean masks (a host read each), tests membership by torch.isin over
+// Cantor-paired keys and scatters the gradient with two index_add_ launches of float atomics.  Here one call serves every link
+// task of the step (staff and voice: different features, different candidates), as a table.
+//
+// agnn_link_bce_fwd_f32: a group of G lanes (G = 4 .. 64, the power of two covering H / 4 float4 columns; a whole wave at H = 256,
+//   several column passes above it) owns one candidate: both rows are read once as float4, the products are summed in a fixed
+//   order (per lane over its columns, then a butterfly over the group), the row of the true relation's by-source CSR is scanned
+//   for d by the same lanes.  A workgroup owns a tile of 64 candidates; wave 0 then takes one candidate per lane for the BCE and
+//   the stores, and the tile's loss sum and five integer counts (alive, tp, fp, fn, tn) go to a partial slot; a second kernel of
+//   one workgroup per task adds the slots in a fixed order: two runs give
+//   the same bits, and nothing is added atomically.  Candidates with an end outside [0, limit) are not alive: no row is read for
+//   them, logit 0, label 0, g 0 — the reference's mask compactions (:712-717) without their host reads.
+// agnn_link_bce_bwd_f32: dz[i] = scale (sum_{e: s_e = i} g_e z[d_e] + sum_{e: d_e = i} g_e z[s_e]) as a gather-reduce over the
+//   candidate list's two CSRs, one row of dz per group, the coefficient fetched through `perm`: every row is written exactly
+//   once (no zero fill, no atomics); a self loop appears in both CSRs and so contributes 2 g_e z[i].
+#include <cmath>
+
+#include "agnn_common.h"
+
+namespace {
+
+constexpr int kTile = 64;       // candidates per workgroup (one lane of wave 0 each in the tile's reduction)
+constexpr int kPartWords = 6;   // loss sum (float bits) | alive, tp, fp, fn, tn
+constexpr int kU = 4;           // list entries a group of the backward keeps in flight
+
+struct LinkFwdDev {
+  const float* z;
+  int64_t ld_z;
+  const int64_t* src;
+  const int64_t* dst;
+  const int32_t* t_rowptr;
+  const int32_t* t_col;
+  float* logit;
+  uint8_t* label;
+  float* g;
+  int32_t E, limit, tile0, pad;
+};
+struct LinkFwdTable {
+  int32_t n_tasks, pad;
+  LinkFwdDev t[AGNN_MAX_SEG];
+};
+
+struct LinkFinalDev {
+  float* loss;
+  float* inv_cnt;
+  int32_t* counts;
+  int32_t tile0, tiles;
+};
+struct LinkFinalTable {
+  LinkFinalDev t[AGNN_MAX_SEG];
+};
+
+struct LinkBwdDev {
+  const float* z;
+  int64_t ld_z;
+  const float* g;
+  const int32_t* s_rowptr;
+  const int32_t* s_col;
+  const int32_t* s_perm;
+  const int32_t* d_rowptr;
+  const int32_t* d_col;
+  const int32_t* d_perm;
+  float* dz;
+  int64_t ld_dz;
+  int32_t n, E, blk0, pad;
+};
+struct LinkBwdTable {
+  int32_t n_tasks, pad;
+  LinkBwdDev t[AGNN_MAX_SEG];
+};
+static_assert(sizeof(LinkFwdTable) + 64 <= 4096 && sizeof(LinkBwdTable) + 64 <= 4096, "the tables travel as kernel arguments");
+
+// log2 of the lanes per candidate / row: the power of two in [4, 64] that covers H4 float4 columns (64 above 64 columns)
+inline int group_log2(int H4) {
+  int lg = 2;
+  while (lg < 6 && (1 << lg) < H4) ++lg;
+  return lg;
+}
+
+__device__ __forceinline__ float group_sum(float v, int G) {
+  for (int m = G >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+__device__ __forceinline__ int group_or(int v, int G) {
+  for (int m = G >> 1; m > 0; m >>= 1) v |= __shfl_xor(v, m);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_link_fwd(LinkFwdTable tab, int H4, int lg, uint32_t* __restrict__ part) {
+  __shared__ float x_s[kTile];
+  __shared__ int flag_s[kTile];
+  const int tid = threadIdx.x;
+  int task = 0;
+  while (task + 1 < tab.n_tasks && static_cast<int>(blockIdx.x) >= tab.t[task + 1].tile0) ++task;
+  const LinkFwdDev& T = tab.t[task];
+  const int tile = static_cast<int>(blockIdx.x) - T.tile0;
+  const int G = 1 << lg, gpb = 256 >> lg;
+  const int grp = tid >> lg, lig = tid & (G - 1);
+  const float* __restrict__ z = T.z;
+  // Instruction issue bounds this launch, not memory latency (four candidates in flight per group made it slower): a group only
+  // gathers and reduces; what one lane per candidate can do — the BCE, the stores — waits for wave 0, one lane per candidate.
+  for (int le = grp; le < kTile; le += gpb) {             // the same trip count for every lane of the workgroup
+    const int64_t e = static_cast<int64_t>(tile) * kTile + le;
+    const bool in = e < T.E;
+    int64_t s = 0, d = 0;
+    if (in) { s = T.src[e]; d = T.dst[e]; }
+    const bool alive = in && s >= 0 && d >= 0 && s < T.limit && d < T.limit;
+    float4 a = agnn::f4_zero();
+    int hit = 0;
+    if (alive) {
+      const float* zs = z + s * T.ld_z;
+      const float* zd = z + d * T.ld_z;
+      for (int c = lig; c < H4; c += G) {
+        const float4 u = *reinterpret_cast<const float4*>(zs + 4 * c);
+        const float4 v = *reinterpret_cast<const float4*>(zd + 4 * c);
+        a.x = fmaf(u.x, v.x, a.x); a.y = fmaf(u.y, v.y, a.y); a.z = fmaf(u.z, v.z, a.z); a.w = fmaf(u.w, v.w, a.w);
+      }
+      const int r1 = T.t_rowptr[s + 1];
+      const int32_t d32 = static_cast<int32_t>(d);
+      for (int j = T.t_rowptr[s] + lig; j < r1; j += G) hit |= (T.t_col[j] == d32) ? 1 : 0;
+    }
+    const float x = group_sum((a.x + a.y) + (a.z + a.w), G);
+    hit = group_or(hit, G);
+    if (lig == 0) {
+      x_s[le] = x;
+      flag_s[le] = (in ? 1 : 0) | (alive ? 2 : 0) | (hit ? 4 : 0);
+    }
+  }
+  __syncthreads();
+  if (tid < kTile) {                                       // wave 0: lane = candidate of the tile
+    const int flag = flag_s[tid];
+    const bool in = flag & 1, alive = flag & 2, hit = flag & 4;
+    const float x = x_s[tid];
+    float loss = 0.f, gg = 0.f;
+    int code = 0;
+    if (alive) {
+      const float y = hit ? 1.f : 0.f;
+      const float t = expf(-fabsf(x));                     // in (0, 1]
+      loss = fmaxf(x, 0.f) - x * y + log1pf(t);
+      const float sg = x >= 0.f ? 1.f / (1.f + t) : t / (1.f + t);
+      gg = sg - y;
+      const bool pos = x > 0.f;
+      code = 1 | ((pos && hit) ? 2 : 0) | ((pos && !hit) ? 4 : 0) | ((!pos && hit) ? 8 : 0) | ((!pos && !hit) ? 16 : 0);
+    }
+    if (in) {
+      const int64_t e = static_cast<int64_t>(tile) * kTile + tid;
+      T.logit[e] = alive ? x : 0.f;
+      T.label[e] = static_cast<uint8_t>((alive && hit) ? 1 : 0);
+      T.g[e] = gg;
+    }
+    const float sum = agnn::wave_sum_dpp(loss);
+    uint32_t* p = part + (static_cast<int64_t>(T.tile0) + tile) * kPartWords;
+    const int c0 = __popcll(__ballot(code & 1)), c1 = __popcll(__ballot(code & 2)), c2 = __popcll(__ballot(code & 4));
+    const int c3 = __popcll(__ballot(code & 8)), c4 = __popcll(__ballot(code & 16));
+    if (tid == 0) {
+      p[0] = __float_as_uint(sum);
+      p[1] = c0; p[2] = c1; p[3] = c2; p[4] = c3; p[5] = c4;
+    }
+  }
+}
+
+// one workgroup per task: the tiles' partial results in a fixed order (lane t takes tiles t, t + 256, ..., then a tree in LDS)
+__global__ __launch_bounds__(256) void k_link_final(LinkFinalTable tab, const uint32_t* __restrict__ part) {
+  __shared__ float f_s[256];
+  __shared__ int i_s[5][256];
+  const int tid = threadIdx.x;
+  const LinkFinalDev& T = tab.t[blockIdx.x];
+  float acc = 0.f;
+  int c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;
+  for (int t = tid; t < T.tiles; t += 256) {
+    const uint32_t* p = part + (static_cast<int64_t>(T.tile0) + t) * kPartWords;
+    acc += __uint_as_float(p[0]);
+    c0 += static_cast<int>(p[1]); c1 += static_cast<int>(p[2]); c2 += static_cast<int>(p[3]);
+    c3 += static_cast<int>(p[4]); c4 += static_cast<int>(p[5]);
+  }
+  f_s[tid] = acc;
+  i_s[0][tid] = c0; i_s[1][tid] = c1; i_s[2][tid] = c2; i_s[3][tid] = c3; i_s[4][tid] = c4;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) {
+      f_s[tid] += f_s[tid + w];
+#pragma unroll
+      for (int k = 0; k < 5; ++k) i_s[k][tid] += i_s[k][tid + w];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const int alive = i_s[0][0];
+    const float inv = alive > 0 ? 1.f / static_cast<float>(alive) : 0.f;
+    T.loss[0] = f_s[0] * inv;
+    T.inv_cnt[0] = inv;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) T.counts[k] = i_s[k][0];
+  }
+}
+
+// sum over row i of one CSR of g[perm] z[col], columns 4 c .. 4 c + 3
+__device__ __forceinline__ void link_row(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int32_t* __restrict__ perm,
+                                         int i, const float* __restrict__ g, const float* __restrict__ z, int64_t ld_z, int n, int E, int c,
+                                         float4& acc) {
+  if (E <= 0) return;                                      // no candidate: g and z may be absent
+  const int r1 = rowptr[i + 1];
+  // kU entries in flight, added in list order as one at a time would be.  The loads are unconditional (an idle slot reads the
+  // row's last entry, a skipped one g[0] / row 0, and drops it): a load under a condition becomes a branch with its own wait.
+  for (int j0 = rowptr[i]; j0 < r1; j0 += kU) {
+    int e[kU], o[kU];
+    float ge[kU];
+    float4 v[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const bool in = j0 + u < r1;
+      const int jc = in ? j0 + u : r1 - 1;
+      const int pe = perm[jc], po = col[jc];
+      e[u] = in ? pe : -1;
+      o[u] = in ? po : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const bool ok = static_cast<unsigned>(e[u]) < static_cast<unsigned>(E) && static_cast<unsigned>(o[u]) < static_cast<unsigned>(n);
+      const float gv = g[ok ? e[u] : 0];
+      ge[u] = ok ? gv : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u)                           // a coefficient of 0 (candidates that are not alive, among them) adds nothing
+      v[u] = *reinterpret_cast<const float4*>(z + static_cast<int64_t>(ge[u] != 0.f ? o[u] : 0) * ld_z + 4 * c);
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      if (ge[u] != 0.f) {
+        acc.x = fmaf(ge[u], v[u].x, acc.x); acc.y = fmaf(ge[u], v[u].y, acc.y);
+        acc.z = fmaf(ge[u], v[u].z, acc.z); acc.w = fmaf(ge[u], v[u].w, acc.w);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_link_bwd(LinkBwdTable tab, int H4, int lg, const float* __restrict__ scale) {
+  const int tid = threadIdx.x;
+  int task = 0;
+  while (task + 1 < tab.n_tasks && static_cast<int>(blockIdx.x) >= tab.t[task + 1].blk0) ++task;
+  const LinkBwdDev& T = tab.t[task];
+  const int G = 1 << lg, gpb = 256 >> lg;
+  const int64_t row = static_cast<int64_t>(static_cast<int>(blockIdx.x) - T.blk0) * gpb + (tid >> lg);
+  if (row >= T.n) return;
+  const int i = static_cast<int>(row);
+  const int lig = tid & (G - 1);
+  const float sc = scale[task];
+  for (int c = lig; c < H4; c += G) {                      // H > 256: the row's lists are walked once per column pass
+    float4 acc = agnn::f4_zero();
+    link_row(T.s_rowptr, T.s_col, T.s_perm, i, T.g, T.z, T.ld_z, T.n, T.E, c, acc);
+    link_row(T.d_rowptr, T.d_col, T.d_perm, i, T.g, T.z, T.ld_z, T.n, T.E, c, acc);
+    *reinterpret_cast<float4*>(T.dz + row * T.ld_dz + 4 * c) = make_float4(sc * acc.x, sc * acc.y, sc * acc.z, sc * acc.w);
+  }
+}
+
+int check_h(const char* who, int32_t H) {
+  if (H < 4 || H % 4 != 0) return agnn::fail(AGNN_EINVAL, "%s: H=%d must be a positive multiple of 4", who, H);
+  return AGNN_OK;
+}
+
+int check_fwd_task(const agnn_link_task_t& t, int i, int32_t H) {
+  using namespace agnn;
+  const char* who = "link_bce_fwd";
+  if (t.E < 0 || t.E > INT32_MAX - kTile) return fail(AGNN_EINVAL, "%s: task %d: E=%lld must be in [0, 2^31 - 64)", who, i, (long long)t.E);
+  if (t.n < 0 || t.n > INT32_MAX) return fail(AGNN_EINVAL, "%s: task %d: n=%lld must be in [0, 2^31)", who, i, (long long)t.n);
+  if (t.limit < 0 || t.limit > t.n) return fail(AGNN_EINVAL, "%s: task %d: limit=%lld must be in [0, n=%lld]", who, i, (long long)t.limit, (long long)t.n);
+  if (!t.loss || !t.inv_cnt || !t.counts) return fail(AGNN_EINVAL, "%s: task %d: loss / inv_cnt / counts is null", who, i);
+  if (t.E == 0) return AGNN_OK;
+  if (!t.src || !t.dst) return fail(AGNN_EINVAL, "%s: task %d: src / dst is null", who, i);
+  if (!t.logit || !t.label || !t.g) return fail(AGNN_EINVAL, "%s: task %d: logit / label / g is null", who, i);
+  if (t.limit == 0) return AGNN_OK;                        // no candidate is alive: no row is read
+  if (!t.z) return fail(AGNN_EINVAL, "%s: task %d: z is null", who, i);
+  if (!t.t_rowptr || !t.t_col) return fail(AGNN_EINVAL, "%s: task %d: t_rowptr / t_col is null", who, i);
+  if (t.ld_z < H) return fail(AGNN_EINVAL, "%s: task %d: ld_z=%lld < H=%d", who, i, (long long)t.ld_z, H);
+  if (t.ld_z % 4 != 0) return fail(AGNN_EALIGN, "%s: task %d: ld_z=%lld is not a multiple of 4", who, i, (long long)t.ld_z);
+  if (!aligned16(t.z)) return fail(AGNN_EALIGN, "%s: task %d: z is not 16-byte aligned", who, i);
+  return AGNN_OK;
+}
+
+int64_t fwd_tiles(int32_t n_tasks, const agnn_link_task_t* tasks) {
+  int64_t tiles = 0;
+  for (int i = 0; i < n_tasks; ++i) tiles += tasks[i].E > 0 ? (tasks[i].E + kTile - 1) / kTile : 0;
+  return tiles;
+}
+
+}  // namespace
+
+extern "C" size_t agnn_link_bce_workspace_bytes(int32_t n_tasks, const agnn_link_task_t* tasks) {
+  if (n_tasks <= 0 || n_tasks > AGNN_MAX_SEG || !tasks) return 0;
+  return static_cast<size_t>(fwd_tiles(n_tasks, tasks)) * kPartWords * sizeof(uint32_t);
+}
+
+extern "C" int agnn_link_bce_fwd_f32(int32_t n_tasks, const agnn_link_task_t* tasks, int32_t H, void* workspace, size_t workspace_bytes,
+                                     agnn_stream_t stream_) {
+  using namespace agnn;
+  if (int rc = check_h("link_bce_fwd", H)) return rc;
+  if (n_tasks < 0 || n_tasks > AGNN_MAX_SEG) return fail(AGNN_EINVAL, "link_bce_fwd: n_tasks=%d must be in [0, %d]", n_tasks, AGNN_MAX_SEG);
+  if (n_tasks == 0) return AGNN_OK;
+  if (!tasks) return fail(AGNN_EINVAL, "link_bce_fwd: tasks is null");
+  LinkFwdTable tab;
+  LinkFinalTable fin;
+  tab.n_tasks = n_tasks;
+  tab.pad = 0;
+  int64_t tiles = 0;
+  for (int i = 0; i < n_tasks; ++i) {
+    const agnn_link_task_t& t = tasks[i];
+    if (int rc = check_fwd_task(t, i, H)) return rc;
+    const int64_t nt = t.E > 0 ? (t.E + kTile - 1) / kTile : 0;
+    if (tiles + nt > INT32_MAX) return fail(AGNN_EINVAL, "link_bce_fwd: more than 2^31 - 1 tiles of candidates");
+    tab.t[i] = LinkFwdDev{t.z, t.ld_z, t.src, t.dst, t.t_rowptr, t.t_col, t.logit, t.label, t.g, static_cast<int32_t>(t.E),
+                          static_cast<int32_t>(t.limit), static_cast<int32_t>(tiles), 0};
+    fin.t[i] = LinkFinalDev{t.loss, t.inv_cnt, t.counts, static_cast<int32_t>(tiles), static_cast<int32_t>(nt)};
+    tiles += nt;
+  }
+  const size_t need = static_cast<size_t>(tiles) * kPartWords * sizeof(uint32_t);
+  if (tiles > 0) {
+    if (!workspace) return fail(AGNN_EINVAL, "link_bce_fwd: workspace is null");
+    if (workspace_bytes < need) return fail(AGNN_ENOMEM, "link_bce_fwd: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((reinterpret_cast<uintptr_t>(workspace) & 3u) != 0) return fail(AGNN_EALIGN, "link_bce_fwd: workspace is not 4-byte aligned");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  uint32_t* part = static_cast<uint32_t*>(workspace);
+  if (tiles > 0) {
+    hipLaunchKernelGGL(k_link_fwd, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, s, tab, H / 4, group_log2(H / 4), part);
+    if (int rc = check_launch("link_bce_fwd")) return rc;
+  }
+  hipLaunchKernelGGL(k_link_final, dim3(static_cast<unsigned>(n_tasks)), dim3(256), 0, s, fin, part);
+  return check_launch("link_bce_fwd (final pass)");
+}
+
+extern "C" int agnn_link_bce_bwd_f32(int32_t n_tasks, const agnn_link_bwd_t* tasks, int32_t H, const float* scale, agnn_stream_t stream_) {
+  using namespace agnn;
+  const char* who = "link_bce_bwd";
+  if (int rc = check_h(who, H)) return rc;
+  if (n_tasks < 0 || n_tasks > AGNN_MAX_SEG) return fail(AGNN_EINVAL, "%s: n_tasks=%d must be in [0, %d]", who, n_tasks, AGNN_MAX_SEG);
+  if (n_tasks == 0) return AGNN_OK;
+  if (!tasks) return fail(AGNN_EINVAL, "%s: tasks is null", who);
+  LinkBwdTable tab;
+  tab.n_tasks = n_tasks;
+  tab.pad = 0;
+  const int lg = group_log2(H / 4), gpb = 256 >> lg;
+  int64_t blocks = 0;
+  for (int i = 0; i < n_tasks; ++i) {
+    const agnn_link_bwd_t& t = tasks[i];
+    if (t.n < 0 || t.n > INT32_MAX) return fail(AGNN_EINVAL, "%s: task %d: n=%lld must be in [0, 2^31)", who, i, (long long)t.n);
+    if (t.E < 0 || t.E > INT32_MAX) return fail(AGNN_EINVAL, "%s: task %d: E=%lld must be in [0, 2^31)", who, i, (long long)t.E);
+    const int64_t nb = (t.n + gpb - 1) / gpb;
+    if (t.n > 0) {
+      if (!t.dz) return fail(AGNN_EINVAL, "%s: task %d: dz is null", who, i);
+      if (!t.s_rowptr || !t.d_rowptr) return fail(AGNN_EINVAL, "%s: task %d: s_rowptr / d_rowptr is null", who, i);
+      if (t.ld_dz < H) return fail(AGNN_EINVAL, "%s: task %d: ld_dz=%lld < H=%d", who, i, (long long)t.ld_dz, H);
+      if (t.ld_dz % 4 != 0) return fail(AGNN_EALIGN, "%s: task %d: ld_dz=%lld is not a multiple of 4", who, i, (long long)t.ld_dz);
+      if (!aligned16(t.dz)) return fail(AGNN_EALIGN, "%s: task %d: dz is not 16-byte aligned", who, i);
+      if (t.E > 0) {
+        if (!t.z || !t.g) return fail(AGNN_EINVAL, "%s: task %d: z / g is null", who, i);
+        if (!t.s_col || !t.s_perm || !t.d_col || !t.d_perm) return fail(AGNN_EINVAL, "%s: task %d: a col / perm array is null", who, i);
+        if (t.ld_z < H) return fail(AGNN_EINVAL, "%s: task %d: ld_z=%lld < H=%d", who, i, (long long)t.ld_z, H);
+        if (t.ld_z % 4 != 0) return fail(AGNN_EALIGN, "%s: task %d: ld_z=%lld is not a multiple of 4", who, i, (long long)t.ld_z);
+        if (!aligned16(t.z)) return fail(AGNN_EALIGN, "%s: task %d: z is not 16-byte aligned", who, i);
+      }
+    }
+    if (blocks + nb > INT32_MAX) return fail(AGNN_EINVAL, "%s: more than 2^31 - 1 workgroups", who);
+    tab.t[i] = LinkBwdDev{t.z, t.ld_z, t.g, t.s_rowptr, t.s_col, t.s_perm, t.d_rowptr, t.d_col, t.d_perm, t.dz, t.ld_dz,
+                          static_cast<int32_t>(t.n), static_cast<int32_t>(t.E), static_cast<int32_t>(blocks), 0};
+    blocks += nb;
+  }
+  if (blocks == 0) return AGNN_OK;
+  if (!scale) return fail(AGNN_EINVAL, "%s: scale is null", who);
+  hipLaunchKernelGGL(k_link_bwd, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream_), tab, H / 4, lg, scale);
+  return check_launch(who);
+}

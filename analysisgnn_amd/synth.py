@@ -306,6 +306,49 @@ def make_sampled_batch(n_graphs: int, n_targets: int = 500, num_neighbors: Seque
                                       seed=sd, first_target=first_target) for sd in seeds])
 
 
+def add_staff_voice(g: ScoreGraph, seed: int = 0) -> ScoreGraph:
+    """`g` with the two relations the pretraining stage predicts (models/analysis.py:709-710), for a whole or collated graph; `g`
+    itself is left as it is.  Every note draws a MIDI pitch (seeded; `extras["pitch"]`) and sits on staff 0 below pitch 60, staff
+    1 from there on (`extras["staff"]`).
+
+    * ``staff``  the onset and consecutive pairs (i, j), in that order, whose notes share a staff; duplicates between the two lists
+                 are kept out, the self loops of `onset` stay.
+    * ``voice``  a subset of the consecutive edges that forms chains: walking the notes in order, a note continues into the free
+                 successor (one no other chain has taken) nearest in pitch on its own staff, if there is one — at most one
+                 successor and one predecessor per note."""
+    rng = np.random.default_rng(seed)
+    n = g.num_nodes["note"]
+    pitch = rng.integers(36, 85, size=n).astype(np.int64)
+    staff = (pitch >= 60).astype(np.int64)
+    onset = g.edge_index[("note", "onset", "note")]
+    cons = g.edge_index[("note", "consecutive", "note")]
+    both = np.concatenate([onset, cons], axis=1)
+    both = both[:, staff[both[0]] == staff[both[1]]]
+    _, first = np.unique(both[0] * max(n, 1) + both[1], return_index=True)
+    staff_e = both[:, np.sort(first)]
+    succ: Dict[int, List[int]] = {}
+    for s, d in zip(cons[0].tolist(), cons[1].tolist()):
+        succ.setdefault(s, []).append(d)
+    taken = np.zeros(n, dtype=bool)
+    vs: List[int] = []
+    vd: List[int] = []
+    for i in range(n):
+        free = [j for j in succ.get(i, []) if not taken[j] and staff[j] == staff[i] and j != i]
+        if free:
+            j = min(free, key=lambda c: (abs(int(pitch[c]) - int(pitch[i])), c))
+            taken[j] = True
+            vs.append(i)
+            vd.append(j)
+    ei = dict(g.edge_index)
+    ei[("note", "staff", "note")] = np.ascontiguousarray(staff_e, dtype=np.int64)
+    ei[("note", "voice", "note")] = np.asarray([vs, vd], dtype=np.int64).reshape(2, -1)
+    extras = dict(g.extras)
+    extras["pitch"], extras["staff"] = pitch, staff
+    return ScoreGraph(num_nodes=dict(g.num_nodes), edge_index=ei, batch=dict(g.batch), onset_div=g.onset_div, duration_div=g.duration_div,
+                      num_graphs=g.num_graphs, num_sampled_nodes=g.num_sampled_nodes, num_sampled_edges=g.num_sampled_edges,
+                      batch_size=g.batch_size, extras=extras)
+
+
 def torch_inputs(g: ScoreGraph, in_channels: int = 25, device="cpu", seed: int = 0):
     """Tensors in the HeteroData layout `TorchAnalysisGNN.encode` consumes:
     x_dict ~ N(0,1) float32, int64 COO edge_index_dict, batch_dict, pitch_spelling ~ U{0..34},

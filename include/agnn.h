@@ -36,6 +36,8 @@
  *   agnn_hgt_attn_*       PyG `HGTConv` message/softmax/aggregate, reached through graphmuse
  *                         `HybridHGT` (ref: models/analysis.py:445-453)
  *   agnn_taskattn_*       `CrossTaskTransformer`: attention over the task tokens of every note (ref: models/analysis.py:408-418)
+ *   agnn_link_bce_*       the staff / voice link prediction of the pretraining stage: endpoint gathers, dot product,
+ *                         BCEWithLogitsLoss, pair membership and the index_add_ backward (ref: models/analysis.py:397-401, :704-731)
  *
  * Conventions (all entry points)
  *   - plain pointers and sizes only; every `const T*`/`T*` marked (device) is device memory owned
@@ -1076,6 +1078,67 @@ int agnn_smote_synth_bwd_f32(const float* g, int64_t ld_g, int64_t N, int32_t D,
                              int64_t ld_w, agnn_stream_t stream);
 int agnn_smote_draws_f32(int64_t S, int32_t D, int32_t k, const int64_t* rng, uint32_t call_id, int32_t* choice, float* gap,
                          agnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Link prediction of the pretraining stage (ref: models/analysis.py:360-406 `PreEncoder`, :697-744 `PreEncoderPL._common_step`;
+ * csrc/linkpred.hip): candidate edges scored by the dot product of their endpoint rows, BCEWithLogitsLoss against membership in
+ * a true relation.  One call serves a table (HOST, read during the call) of at most AGNN_MAX_SEG tasks with their own features,
+ * candidates and true relations; H is shared.  H % 4 == 0, rows 16-byte aligned, leading dimensions multiples of 4 floats:
+ * AGNN_EINVAL / AGNN_EALIGN before any HIP call otherwise, as for NULL pointers, negative sizes and limit > n.  No float
+ * atomics; two runs give the same bits.
+ *
+ * agnn_link_bce_fwd_f32:  for candidate e = (src[e], dst[e]) (int64, rows 0 and 1 of a PyG edge_index) of a task
+ *     alive_e = 0 <= src, dst < limit         (limit <= n: the batch's target rows; the reference's mask compactions :712-717)
+ *     logit_e = <z[src], z[dst]>              label_e = 1 iff dst occurs in row src of the true relation's by-source CSR
+ *     loss_e  = max(x, 0) - x y + log1p(exp(-|x|))                 g_e = sigmoid(x) - y
+ *   (t_rowptr: n + 1 offsets into t_col, as agnn_csr_build lays them out; duplicate true edges are harmless).  A candidate that
+ *   is not alive reads no row and gets logit 0, label 0, g 0.  Per task: loss[0] = sum of loss_e / alive count, inv_cnt[0] =
+ *   1 / alive count, counts[5] = alive, tp, fp, fn, tn with "predicted positive" = logit > 0.  A task without an alive candidate
+ *   gets loss 0 and inv_cnt 0 (torch's BCEWithLogitsLoss over nothing: NaN).  The loss is summed per tile of 64 candidates into
+ *   the workspace (agnn_link_bce_workspace_bytes) and the tiles by one workgroup per task, both in a fixed order.  Tasks with
+ *   E == 0 look at no candidate pointer.
+ * agnn_link_bce_bwd_f32:  dz[i] = scale[task] (sum_{e: src_e = i} g_e z[dst_e] + sum_{e: dst_e = i} g_e z[src_e]) for every row
+ *   i < n, from the candidate list's CSR by source (s_*: col = destination) and by destination (d_*: col = source), perm = the
+ *   candidate's position (agnn_csr_build).  scale: (device) one float per task, the incoming gradient times inv_cnt.  Every row
+ *   of dz is written exactly once (rows without a candidate: zeros); a self loop lies in both CSRs and contributes 2 g_e z[i].
+ *   Entries whose col or perm is out of range are skipped.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const float* z;          /* (device) [n, H], row stride ld_z */
+  int64_t ld_z;
+  int64_t n;
+  const int64_t* src;      /* (device) [E] */
+  const int64_t* dst;      /* (device) [E] */
+  int64_t E;
+  int64_t limit;
+  const int32_t* t_rowptr; /* (device) [n + 1] */
+  const int32_t* t_col;    /* (device) */
+  float* logit;            /* (device) [E] */
+  uint8_t* label;          /* (device) [E] */
+  float* g;                /* (device) [E] */
+  float* loss;             /* (device) [1] */
+  float* inv_cnt;          /* (device) [1] */
+  int32_t* counts;         /* (device) [5] */
+} agnn_link_task_t;
+typedef struct {
+  const float* z;          /* (device) [n, H], row stride ld_z */
+  int64_t ld_z;
+  int64_t n;
+  const float* g;          /* (device) [E] */
+  int64_t E;
+  const int32_t* s_rowptr; /* (device) [n + 1] */
+  const int32_t* s_col;
+  const int32_t* s_perm;
+  const int32_t* d_rowptr; /* (device) [n + 1] */
+  const int32_t* d_col;
+  const int32_t* d_perm;
+  float* dz;               /* (device) [n, H], row stride ld_dz */
+  int64_t ld_dz;
+} agnn_link_bwd_t;
+size_t agnn_link_bce_workspace_bytes(int32_t n_tasks, const agnn_link_task_t* tasks);
+int agnn_link_bce_fwd_f32(int32_t n_tasks, const agnn_link_task_t* tasks, int32_t H, void* workspace, size_t workspace_bytes,
+                          agnn_stream_t stream);
+int agnn_link_bce_bwd_f32(int32_t n_tasks, const agnn_link_bwd_t* tasks, int32_t H, const float* scale, agnn_stream_t stream);
 
 #ifdef __cplusplus
 }
