@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void k_wgrad(WgArgs a) { wgrad_tile(a, blockId
 // pending TOGETHER at the encoder's flush points, so they are issued together: the workgroups of all items fill the chip, every
 // item gets by with the same few slices (384 / total tiles: 5 at the GNN stack's flush), K loops of thousands of rows, and ONE
 // reduction launch serves all outputs.
-constexpr int kWgBatchMax = 24;       // 16 products, of which up to 8 may come as two column-block items (linear.weight_grad_batch)
+constexpr int kWgBatchMax = AGNN_WGRAD_BATCH_MAX_ITEMS;   // 16 products, of which up to 8 may come as two column-block items (linear.weight_grad_batch)
 
 struct WgBatch {
   WgArgs it[kWgBatchMax];

@@ -52,7 +52,6 @@ def embedding(idx: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
 # Fused note-input assembly: cat([x, table_0[idx_0], table_1[idx_1], ...]) in ONE launch, rows padded to 16 bytes, and the
 # tables' gradients in two (csrc/embed.hip).  ref: models/analysis.py:574.
 # ------------------------------------------------------------------------------------------------------------
-MAX_TABLES = 4
 
 
 def _ptr_array(ts):
@@ -105,7 +104,7 @@ def embed_cat(x: torch.Tensor, idxs: Sequence[torch.Tensor], tables: Sequence[to
     buffer whose rows are padded to a multiple of 4 floats (zeros), which is what the projection that follows wants.
     The feature matrix x gets no gradient (it is an input)."""
     n_tab = len(tables)
-    fits = (x.is_cuda and x.dim() == 2 and 1 <= n_tab <= MAX_TABLES and len(idxs) == n_tab and not x.requires_grad
+    fits = (x.is_cuda and x.dim() == 2 and 1 <= n_tab <= _lib.EMBED_MAX_TABLES and len(idxs) == n_tab and not x.requires_grad
             and all(t.dim() == 2 and t.shape[1] == tables[0].shape[1] and t.dtype == torch.float32 for t in tables)
             and tables[0].shape[1] % 2 == 0 and all(i.dim() == 1 and i.shape[0] == x.shape[0] for i in idxs))
     if not fits:

@@ -42,6 +42,9 @@
  * Conventions (all entry points)
  *   - plain pointers and sizes only; every `const T*`/`T*` marked (device) is device memory owned
  *     by the caller (PyTorch's caching allocator); arrays marked (host) are read during the call.
+ *   - this file is READ by the Python binding (analysisgnn_amd/_abi.py), which accepts the forms used here and nothing else.  A
+ *     comment that begins with (host) behind a parameter is part of the contract: it makes a scalar or pointer array a typed host
+ *     array there (POINTER(int32) ...); every other non-struct pointer is an address (c_void_p).
  *   - all work is enqueued on `stream`; no implicit synchronisation, no default-stream use, no
  *     allocation, no global mutable state: safe to call from several host threads and under
  *     hipGraph capture.
@@ -441,9 +444,11 @@ int agnn_wgrad_f32(const float* dy, int64_t ld_dy, const float* x, int64_t ld_x,
 /* Several weight gradients in ONE launch pair (product kernel + slab reduction): the items' workgroups fill the chip together, so
  * every item gets by with a few row slices instead of up to 64 (fewer slabs written and read back, longer K loops) and the
  * step's ~20 reduction launches become one per group.  Same arithmetic per item as agnn_wgrad_f32 with that slice count
- * (deterministic; the slice count — hence the summation order — depends on the group's composition).  At most 24 items: the host
- * groups 16 products, and a product whose input lies in two column blocks comes as two items (same tiles, same slices, same bits
- * as the one item on the concatenation when the blocks are multiples of the 128-column tile). */
+ * (deterministic; the slice count — hence the summation order — depends on the group's composition).  At most
+ * AGNN_WGRAD_BATCH_MAX_ITEMS items: the host groups 16 products, and a product whose input lies in two column blocks comes as two
+ * items (same tiles, same slices, same bits as the one item on the concatenation when the blocks are multiples of the 128-column
+ * tile). */
+#define AGNN_WGRAD_BATCH_MAX_ITEMS 24
 typedef struct {
   const float* dy;   /* (device) [n, out_f], leading dimension ld_dy */
   const float* x;    /* (device) [n, in_f],  leading dimension ld_x  */
@@ -486,7 +491,7 @@ int agnn_pack_f32(int32_t n_items, const agnn_pack_item_t* items /* (host) */, a
  *   * Product kernel, tiles, row slices, slab layout and summation order are those of agnn_wgrad_batch_f32 on the same operand
  *     list; a column sum has the bits of agnn_norm_act_colsum_f32.  No atomics.
  *   * Destinations of one call must not overlap, except records of one product that name the same column range at the same
- *     address with the same ld (they receive the same values): AGNN_EINVAL.  n_items <= 24, n_sums <= AGNN_GRAD_MAX_SUMS; both zero: AGNN_OK, nothing is launched.
+ *     address with the same ld (they receive the same values): AGNN_EINVAL.  n_items <= AGNN_WGRAD_BATCH_MAX_ITEMS, n_sums <= AGNN_GRAD_MAX_SUMS; both zero: AGNN_OK, nothing is launched.
  * ------------------------------------------------------------------------------------------ */
 #define AGNN_GRAD_MAX_SUMS 16   /* column sums per agnn_grad_epilogue_f32 call */
 typedef struct {
@@ -539,11 +544,11 @@ int agnn_debug_stamp(uint64_t* slot /* (device) */, agnn_stream_t stream);
  * ------------------------------------------------------------------------------------------ */
 #define AGNN_EMBED_MAX_TABLES 4
 int agnn_embed_cat_fwd_f32(const float* x, int64_t ld_x, int32_t in_x, int64_t n_rows, int32_t n_tab,
-                           const int64_t* const* idx, const float* const* tables, const int32_t* vocab, int32_t dim,
-                           float* out, int64_t ld_out, agnn_stream_t stream);
-size_t agnn_embed_workspace_bytes(int32_t n_tab, const int32_t* vocab, int32_t dim);
+                           const int64_t* const* idx /* (host) */, const float* const* tables /* (host) */,
+                           const int32_t* vocab /* (host) */, int32_t dim, float* out, int64_t ld_out, agnn_stream_t stream);
+size_t agnn_embed_workspace_bytes(int32_t n_tab, const int32_t* vocab /* (host) */, int32_t dim);
 int agnn_embed_cat_bwd_f32(const float* dout, int64_t ld_dout, int32_t col0, int64_t n_rows, int32_t n_tab,
-                           const int64_t* const* idx, const int32_t* vocab, int32_t dim, float* dtables,
+                           const int64_t* const* idx /* (host) */, const int32_t* vocab /* (host) */, int32_t dim, float* dtables,
                            void* workspace, size_t workspace_bytes, agnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -557,7 +562,7 @@ int agnn_embed_cat_bwd_f32(const float* dout, int64_t ld_dout, int32_t col0, int
  * ------------------------------------------------------------------------------------------ */
 int agnn_heads_fwd_f32(const float* x, int64_t ld_x, int64_t n_rows, int32_t in_f, int32_t hidden, int32_t T, const float* w1,
                        const float* b1, const float* gamma, const float* beta, float eps, const float* w2, const float* b2,
-                       const int32_t* offs_dev, const int32_t* offs_host, float* z, float* y, int64_t ld_h, float* mean,
+                       const int32_t* offs_dev, const int32_t* offs_host /* (host) */, float* z, float* y, int64_t ld_h, float* mean,
                        float* rstd, float* logits, int64_t ld_o, agnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -1067,8 +1072,9 @@ typedef struct {
   int64_t label[AGNN_MAX_SEG];
 } agnn_smote_plan_t;
 int agnn_rowsel_f32(const float* q, int64_t ld_q, const int32_t* q_rows, int64_t q_n, const float* c, int64_t ld_c,
-                    const int32_t* c_rows, int64_t c_n, int32_t n_seg, const int32_t* q_off, const int32_t* c_off, int32_t D,
-                    int32_t ksel, int32_t mode, int32_t* idx, float* score, agnn_stream_t stream);
+                    const int32_t* c_rows, int64_t c_n, int32_t n_seg, const int32_t* q_off /* (host) */,
+                    const int32_t* c_off /* (host) */, int32_t D, int32_t ksel, int32_t mode, int32_t* idx, float* score,
+                    agnn_stream_t stream);
 int agnn_smote_synth_fwd_f32(const float* x, int64_t ld_x, const int64_t* y, int64_t N, int32_t D, const agnn_smote_plan_t* plan,
                              const int32_t* rows, const int32_t* nbr, int32_t ld_nbr, int32_t k, const int32_t* choice,
                              const float* gap, const int64_t* rng, uint32_t call_id, float* x_over, int64_t ld_over,
