@@ -165,7 +165,7 @@ int gated_check(const char* who, const agnn_gated_t* g) {
   if (g->n_rows < 0 || g->n_rows >= (int64_t{1} << 31)) return fail(AGNN_EINVAL, "%s: n_rows=%lld", who, (long long)g->n_rows);
   if (g->H <= 0 || (g->H & 3) || g->H > 1024) return fail(AGNN_EINVAL, "%s: H=%d must be a multiple of 4 in [4,1024]", who, g->H);
   if (g->n_rows == 0) return 1;
-  if (!g->rowptr || !g->a || !g->b || !g->h) return fail(AGNN_EINVAL, "%s: null argument", who);
+  if (!g->rowptr || !g->col || !g->a || !g->b || !g->h) return fail(AGNN_EINVAL, "%s: null argument", who);
   if (!aligned16(g->a) || !aligned16(g->b) || !aligned16(g->h) || (g->ld & 3) || g->ld < g->H) return fail(AGNN_EALIGN, "%s: a/b/h misaligned or ld < H", who);
   if (g->c && (!aligned16(g->c) || (g->ld_c & 3) || g->ld_c < g->H || !g->perm)) return fail(AGNN_EALIGN, "%s: per-edge term misaligned or perm missing", who);
   return 0;
@@ -189,7 +189,7 @@ inline GatedArgs to_args(const agnn_gated_t* g) {
 extern "C" int agnn_gated_fwd_f32(const agnn_gated_t* g, float* out, int64_t ld_out, agnn_stream_t stream_) {
   using namespace agnn;
   if (int rc = gated_check("gated_fwd", g)) return rc > 0 ? AGNN_OK : rc;
-  if (!out || !aligned16(out) || (ld_out & 3)) return fail(AGNN_EALIGN, "gated_fwd: out misaligned");
+  if (!out || !aligned16(out) || (ld_out & 3) || ld_out < g->H) return fail(AGNN_EALIGN, "gated_fwd: out misaligned or ld_out < H");
   AGNN_GATED_LAUNCH(k_gated_fwd, out, ld_out);
   return check_launch("gated_fwd");
 }
@@ -198,7 +198,8 @@ extern "C" int agnn_gated_bwd_dst_f32(const agnn_gated_t* g, const float* ds, in
                                       agnn_stream_t stream_) {
   using namespace agnn;
   if (int rc = gated_check("gated_bwd_dst", g)) return rc > 0 ? AGNN_OK : rc;
-  if (!ds || !da || !aligned16(ds) || !aligned16(da) || (ld_ds & 3) || !g->perm) return fail(AGNN_EALIGN, "gated_bwd_dst: ds/da misaligned or perm missing");
+  if (!ds || !da || !aligned16(ds) || !aligned16(da) || (ld_ds & 3) || ld_ds < g->H || !g->perm) return fail(AGNN_EALIGN, "gated_bwd_dst: ds/da misaligned, ld_ds < H or perm missing");
+  if (dc && (!g->c || !aligned16(dc))) return fail(AGNN_EALIGN, "gated_bwd_dst: dc misaligned or given without the per-edge term c (dc shares ld_c)");
   AGNN_GATED_LAUNCH(k_gated_bwd_dst, ds, ld_ds, da, dc);
   return check_launch("gated_bwd_dst");
 }
@@ -207,7 +208,7 @@ extern "C" int agnn_gated_bwd_src_f32(const agnn_gated_t* g, const float* ds, in
                                       agnn_stream_t stream_) {
   using namespace agnn;
   if (int rc = gated_check("gated_bwd_src", g)) return rc > 0 ? AGNN_OK : rc;
-  if (!ds || !db || !dh || !aligned16(ds) || !aligned16(db) || !aligned16(dh) || (ld_ds & 3) || !g->perm) return fail(AGNN_EALIGN, "gated_bwd_src: misaligned or perm missing");
+  if (!ds || !db || !dh || !aligned16(ds) || !aligned16(db) || !aligned16(dh) || (ld_ds & 3) || ld_ds < g->H || !g->perm) return fail(AGNN_EALIGN, "gated_bwd_src: misaligned, ld_ds < H or perm missing");
   AGNN_GATED_LAUNCH(k_gated_bwd_src, ds, ld_ds, db, dh);
   return check_launch("gated_bwd_src");
 }

@@ -318,6 +318,9 @@ int agnn_hgt_attn_bwd_src_batch_f32(int32_t n_items, const agnn_hgt_src_item_t* 
  * bwd_src takes the TRANSPOSED CSR (b, h indexed by row; a and dS by col).  Same a/b/h/c pointers in all calls.
  *   bwd_dst: da_i = sum_e dS_i h_j z(1-z)   and, when dc != NULL, dc[perm[p]] = that summand
  *   bwd_src: db_j = sum_e dS_i h_j z(1-z),  dh_j = sum_e z dS_i
+ * da, db, dh have the leading dimension ld of a / b / h, dc that of c (ld_c; dc needs c).  H % 4 == 0, H <= 1024; every
+ * pointer 16-byte aligned, every leading dimension a multiple of 4 and >= H (ld_out and ld_ds included), rowptr / col /
+ * a / b / h non-NULL: AGNN_EINVAL / AGNN_EALIGN otherwise, before any launch.  n_rows == 0: success, nothing is read.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   const int32_t* rowptr;  /* (device) [n_rows + 1] */

@@ -82,7 +82,11 @@ def test_rowend_matches_oracle():
 
 
 def _spmm_case(n_dst, n_src, es, H, mean, shared, with_self, skip_self=False, col_limit=None, trim=None, seed=0,
-               colscale=False, root_rows=None):
+               colscale=False, root_rows=None, ew=None, accum=False, variant=None):
+    """ew: True (every relation) or one bool per relation — random per-edge weights in COO order, zeros and negative values
+    among them, brought to CSR position order by ops._perm_weights for the kernel and by the oracle's own `perm` for the
+    oracle.  accum: `out` is prefilled with known random values and AGNN_SPMM_ACCUM is set; expected = prefill + oracle.
+    variant: ops.SPMM_VARIANT for this launch (1024 = AGNN_SPMM_GENERIC, 2048 = AGNN_SPMM_FAST_V4)."""
     from analysisgnn_amd import _lib, ops
     dev = _dev()
     rng = np.random.default_rng(seed)
@@ -95,19 +99,35 @@ def _spmm_case(n_dst, n_src, es, H, mean, shared, with_self, skip_self=False, co
     x = rng.standard_normal((n_dst, H)).astype(np.float32) if with_self else None
     cs = [rng.random(n_src).astype(np.float32) + 0.5 for _ in range(R)] if colscale else [None] * R
     n_rows = n_dst
+    weighted = [bool(ew)] * R if not isinstance(ew, (list, tuple)) else list(ew)
+    ws = []
+    for r in range(R):                                    # drawn after everything above: the unweighted cases keep their data
+        w = None
+        if weighted[r]:
+            w = rng.standard_normal(es[r]).astype(np.float32)
+            w[rng.random(es[r]) < 0.15] = 0.0
+        ws.append(w)
+    prefill = rng.standard_normal((n_rows, H if shared else (R + (root_rows is not None)) * H)).astype(np.float32) if accum else None
     orels, grels, keep = [], [], []
     base = 0
     for r in range(R):
         rp = rs[base:base + n_dst + 1]
         base += n_dst
         re_o = c_oracle.csr_rowend(rp, p, trim[r]) if trim else None
-        orels.append(dict(src=srcs[r], rowptr=rp, col=c, rowend=re_o, colscale=cs[r]))
+        ew_o = ew_g = None
+        if weighted[r]:
+            ew_o = np.zeros(c.size, dtype=np.float32)     # per CSR position, as agnn_rel_t.ew: w of the COO edge perm[pos]
+            ew_o[rp[0]:rp[-1]] = ws[r][p[rp[0]:rp[-1]]]
+            ew_g = ops._perm_weights(csrs[r], torch.from_numpy(ws[r]).to(dev))
+            if es[r] >= 100:
+                assert (ew_o[rp[0]:rp[-1]] == 0).any() and (ew_o[rp[0]:rp[-1]] < 0).any()
+        orels.append(dict(src=srcs[r], rowptr=rp, col=c, rowend=re_o, colscale=cs[r], ew=ew_o))
         st = torch.from_numpy(srcs[r]).to(dev)
         re_g = csrs[r].rowend(trim[r]) if trim else None
         cst = torch.from_numpy(cs[r]).to(dev) if colscale else None
-        keep += [st, re_g, cst]
+        keep += [st, re_g, cst, ew_g]
         grels.append(dict(src=st.data_ptr(), rowptr=csrs[r].rowptr.data_ptr(), rowend=_lib.ptr(re_g),
-                          col=csrs[r].col.data_ptr(), colscale=_lib.ptr(cst), ld_src=st.stride(0)))
+                          col=csrs[r].col.data_ptr(), ew=_lib.ptr(ew_g), colscale=_lib.ptr(cst), ld_src=st.stride(0)))
     lim = col_limit if col_limit is not None else 2 ** 31 - 1
     exp, inv_o = c_oracle.spmm(orels, n_rows, H, 0 if shared else H, self_=None if root_rows is not None else x, mean=mean,
                                skip_self=skip_self, col_limit=lim, want_inv_cnt=True)
@@ -118,13 +138,28 @@ def _spmm_case(n_dst, n_src, es, H, mean, shared, with_self, skip_self=False, co
             exp[:root_rows] += x[:root_rows]
         else:
             exp = np.concatenate([exp, x[:n_rows]], axis=1)
-    out = torch.full((n_rows, H if shared else (R + (root_rows is not None)) * H), float("nan"), device=dev)
+    if any(weighted) and not trim and not skip_self and col_limit is None:
+        # the mean divides by the number of edges, whatever their weights (zero weights included)
+        for r in range(R):
+            deg = np.bincount(segs[r]["row"], minlength=n_dst)[:n_rows]
+            assert np.array_equal(inv_o[r], (1.0 / np.maximum(deg, 1)).astype(np.float32))
+    if accum:
+        exp = prefill + exp                      # one float32 addition per element, as the kernel's (a shared slot: once)
+        out = torch.from_numpy(prefill).to(dev)
+    else:
+        out = torch.full((n_rows, H if shared else (R + (root_rows is not None)) * H), float("nan"), device=dev)
     inv = torch.empty((R, n_rows), device=dev)
     xt = torch.from_numpy(x).to(dev) if with_self else None
     if root_rows is not None and shared:
         xt = xt[:root_rows].contiguous()         # the slot really is shorter than the output
-    flags = (_lib.SPMM_MEAN if mean else 0) | (_lib.SPMM_SKIP_SELF if skip_self else 0)
-    ops._launch(grels, n_rows, H, out, 0 if shared else H, xt, inv, lim, flags, root_rows=root_rows)
+    flags = (_lib.SPMM_MEAN if mean else 0) | (_lib.SPMM_SKIP_SELF if skip_self else 0) | (_lib.SPMM_ACCUM if accum else 0)
+    before = ops.SPMM_VARIANT
+    if variant is not None:
+        ops.SPMM_VARIANT = variant
+    try:
+        ops._launch(grels, n_rows, H, out, 0 if shared else H, xt, inv, lim, flags, root_rows=root_rows)
+    finally:
+        ops.SPMM_VARIANT = before
     torch.cuda.synchronize()
     got = out.cpu().numpy()
     assert not np.isnan(got).any()
@@ -152,6 +187,10 @@ def test_spmm_heavy_row_and_empty_rows():
     # the same through the backward configuration of the fast path (column scales, relations summed into one slot)
     _spmm_case(40, 500, [3000, 70], 256, mean=False, shared=True, with_self=False, seed=4, colscale=True)
     _spmm_case(33, 500, [2500, 0, 9], 512, mean=True, shared=False, with_self=True, seed=5)
+    # the older fast kernel (AGNN_SPMM_FAST_V4, the A/B yardstick of scripts/spmm_ab.py): second and later 64-id batches, an odd tail
+    _spmm_case(40, 500, [3000], 256, mean=True, shared=False, with_self=False, seed=3, variant=2048)
+    _spmm_case(40, 500, [3000, 70], 256, mean=False, shared=True, with_self=False, seed=4, colscale=True, variant=2048)
+    _spmm_case(33, 500, [2500, 0, 9], 512, mean=True, shared=False, with_self=True, seed=5, variant=2048)
 
 
 def test_spmm_filters_and_trim():
@@ -173,15 +212,20 @@ def test_fast_and_generic_kernels_agree():
                 _spmm_case(300, 300, [1500, 2, 700, 0, 90], H, seed=H, **kw)
             finally:
                 ops.SPMM_VARIANT = 0
+            # the older fast kernel (AGNN_SPMM_FAST_V4): 5 relations = one full group of four and a partly filled one, an
+            # empty relation; then rows with more than 64 neighbours
+            _spmm_case(300, 300, [1500, 2, 700, 0, 90], H, seed=H, variant=2048, **kw)
+            _spmm_case(40, 300, [3000, 0, 100, 2500, 7], H, seed=H + 1, variant=2048, **kw)
 
 
 @pytest.mark.parametrize("H", [256, 512])
-@pytest.mark.parametrize("variant", [0, 1024])
+@pytest.mark.parametrize("variant", [0, 1024, 2048])
 def test_fast_path_trimmed_and_filtered(H, variant):
     """What a training step of the reference launches (models/analysis.py:960-961 always passes the per-hop counts, so
     every layer is trimmed): row ends from `rowend` (forward), `rowend` + column limit + 1/deg column scales (backward),
     and the onset pooling's predicates (models/analysis.py:581-584) — through the fast kernel (k_spmm_fast7, FILT and
-    plain) and through the generic one, each against the C oracle."""
+    plain) and through the generic one, each against the C oracle.  AGNN_SPMM_FAST_V4 (2048) asks for the older fast
+    kernel, which knows neither a trim nor a filter: the dispatcher must fall back to the generic kernel and still match."""
     from analysisgnn_amd import ops
     ops.SPMM_VARIANT = variant
     try:
@@ -219,6 +263,66 @@ def test_root_operand_rejects_what_the_kernel_does_not_cover():
     from analysisgnn_amd import _lib
     with pytest.raises(_lib.AgnnError):
         _spmm_case(30, 30, [100], 64, mean=True, shared=False, with_self=True, root_rows=30)
+
+
+def test_root_operand_refuses_edge_weights():
+    """agnn_spmm_root_f32 exists for the specialised kernel only, which reads no per-edge weight: AGNN_EINVAL, nothing launched
+    (the NaN-filled output would otherwise be compared inside _spmm_case)."""
+    from analysisgnn_amd import _lib
+    for ew in (True, [False, True, False]):
+        with pytest.raises(_lib.AgnnError, match=r"agnn_spmm_root_f32 failed \(-22\).*weights"):
+            _spmm_case(64, 64, [200, 30, 90], 256, mean=True, shared=False, with_self=True, root_rows=64, ew=ew)
+
+
+@pytest.mark.parametrize("H", [4, 64, 260, 1024])
+def test_spmm_edge_weights(H):
+    """Per-position weights `ew` (the route of GATConvLayer and AggSpec.edge_weight), zeros and negative values among them:
+    sum and mean (1 / count counts EDGES, checked inside _spmm_case), shared and per-relation slots, an empty relation, times
+    the column scale, under a trim, under both filters, and rows of about 100 weighted edges."""
+    for mean in (True, False):
+        for shared in (True, False):
+            _spmm_case(97, 61, [400, 0, 150], H, mean, shared, with_self=mean, ew=True, seed=H)
+    _spmm_case(97, 61, [400, 150], H, mean=False, shared=True, with_self=False, colscale=True, ew=True, seed=H + 1)
+    _spmm_case(97, 61, [400, 150], H, mean=True, shared=False, with_self=True, colscale=True, ew=[True, False], seed=H + 2)
+    _spmm_case(97, 97, [400, 150], H, mean=True, shared=False, with_self=False, trim=[250, 0], ew=True, seed=H + 3)
+    _spmm_case(97, 97, [600], H, mean=True, shared=True, with_self=True, skip_self=True, col_limit=70, ew=True, seed=H + 4)
+    _spmm_case(97, 97, [600, 300], H, mean=False, shared=True, with_self=False, skip_self=True, col_limit=70, trim=[450, 300],
+               colscale=True, ew=True, seed=H + 5)
+    _spmm_case(9, 200, [900], H, mean=True, shared=False, with_self=False, ew=True, seed=H + 6)
+
+
+@pytest.mark.parametrize("H", [256, 512])
+@pytest.mark.parametrize("variant", [0, 2048])
+def test_spmm_edge_weights_leave_the_fast_path(H, variant):
+    """At the widths of the specialised kernels, which read no `ew`: every relation weighted, and only one of three — the
+    whole launch must go through the generic kernel, the unweighted relations included."""
+    for kw in (dict(mean=True, shared=False, with_self=True), dict(mean=False, shared=True, with_self=False, colscale=True)):
+        _spmm_case(120, 120, [700, 40, 300], H, ew=True, seed=H, variant=variant, **kw)
+        _spmm_case(120, 120, [700, 40, 300], H, ew=[False, True, False], seed=H + 1, variant=variant, **kw)
+        _spmm_case(12, 120, [900, 40, 300], H, ew=[False, False, True], seed=H + 2, variant=variant, **kw)
+
+
+@pytest.mark.parametrize("H", [32, 260])
+def test_spmm_accumulate_generic_kernel(H):
+    """AGNN_SPMM_ACCUM through the generic kernel: the result is added onto known contents — per relation slot, or once
+    onto a shared slot however many relations are summed into it."""
+    _spmm_case(97, 61, [400, 0, 150], H, mean=True, shared=False, with_self=True, accum=True, seed=H)
+    _spmm_case(97, 61, [400, 0, 150], H, mean=False, shared=True, with_self=False, colscale=True, accum=True, seed=H + 1)
+    _spmm_case(97, 97, [400, 150], H, mean=True, shared=True, with_self=True, skip_self=True, col_limit=70, ew=True, accum=True, seed=H + 2)
+
+
+@pytest.mark.parametrize("H", [256, 512])
+def test_spmm_accumulate_reaches_the_older_fast_kernel(H):
+    """AGNN_SPMM_ACCUM at H = 256 / 512 selects k_spmm_fast: shared and per-relation slots (5 relations, one empty, a row of
+    more than 64 neighbours), with the self term, with column scales; under SKIP_SELF, which that kernel does not know, the
+    launch must fall back to the generic kernel and still accumulate."""
+    _spmm_case(300, 300, [1500, 2, 700, 0, 90], H, mean=True, shared=False, with_self=False, accum=True, seed=H)
+    _spmm_case(300, 300, [1500, 2, 700, 0, 90], H, mean=True, shared=False, with_self=True, accum=True, seed=H + 1)
+    _spmm_case(300, 300, [1500, 2, 700, 0, 90], H, mean=True, shared=True, with_self=True, accum=True, seed=H + 2)
+    _spmm_case(300, 300, [1500, 2, 700, 0, 90], H, mean=False, shared=True, with_self=False, colscale=True, accum=True, seed=H + 3)
+    _spmm_case(40, 500, [3000, 70], H, mean=False, shared=False, with_self=False, colscale=True, accum=True, seed=H + 4)
+    _spmm_case(300, 300, [1400], H, mean=True, shared=True, with_self=True, skip_self=True, accum=True, seed=H + 5)
+    _spmm_case(300, 300, [1500, 40], H, mean=True, shared=False, with_self=False, trim=[900, 40], accum=True, seed=H + 6)
 
 
 def test_spmm_c2_shape_against_oracle():
