@@ -127,15 +127,39 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
-def f32c(t: torch.Tensor) -> torch.Tensor:
-    """fp32 with unit inner stride and 16-byte aligned rows (copies only when necessary)."""
+# ---- operand layout: the one statement of what a kernel may read where it lies ("Operand layout") -----------------
+def rows_ok(t: torch.Tensor, vec: int = 4) -> bool:
+    """A float matrix a kernel can read in place with `vec`-float vectors: fp32, 2-D, unit column stride, a leading dimension
+    that is a multiple of the vector and (with more than one row) not smaller than the row, and a vector-aligned base."""
+    return (t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % vec == 0
+            and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]) and t.data_ptr() % (4 * vec) == 0)
+
+
+def rows16(t: torch.Tensor, vec: int = 4) -> torch.Tensor:
+    """`t` itself when rows_ok(t, vec), otherwise a fresh dense copy (never `.contiguous()`: a contiguous view at an odd offset
+    of a flat buffer is returned unchanged by it, and stays misaligned); a width that is no multiple of 4 gets rows padded to
+    one.  `vec=1`: an operand its kernel reads float by float (the grouped projections' [N, sum of classes] side, whose width
+    is whatever the tasks' class counts add up to).  Raises on a wrong dtype or rank."""
     if t.dtype != torch.float32:
         raise AgnnError(f"fp32 expected, got {t.dtype}")
     if t.dim() != 2:
         raise AgnnError(f"2-D feature matrix expected, got shape {tuple(t.shape)}")
-    if t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.data_ptr() % 16 != 0 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    return t
+    if rows_ok(t, vec):
+        return t
+    n, w = t.shape
+    return torch.empty((n, (w + 3) & ~3), dtype=torch.float32, device=t.device)[:, :w].copy_(t)
+
+
+def vec_ok(t: torch.Tensor, vec: int = 4) -> bool:
+    """A parameter vector (gamma, beta, bias, stacked weights passed flat) a kernel can read in place: fp32, dense, base aligned."""
+    return t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % (4 * vec) == 0
+
+
+def vec16(t: torch.Tensor) -> torch.Tensor:
+    """`t` itself when vec_ok(t), otherwise a fresh dense copy.  Raises on a wrong dtype."""
+    if t.dtype != torch.float32:
+        raise AgnnError(f"fp32 expected, got {t.dtype}")
+    return t if vec_ok(t) else t.clone(memory_format=torch.contiguous_format)
 
 
 def make_rels(items: Sequence[dict]):

@@ -121,7 +121,7 @@ class _AttnFn(torch.autograd.Function):
         qkv, o, lse, *used = ctx.saved_tensors
         heads, p, call_id, q_rows = ctx.cfg
         E = o.shape[1]
-        dO = dO if (dO.stride(1) == 1 and dO.stride(0) % 4 == 0 and dO.data_ptr() % 16 == 0 and dO.stride(0) >= E) else dO.contiguous()
+        dO = _lib.rows16(dO)
         dqkv = torch.empty_like(qkv)
         backward_raw(*_blocks(qkv, E), heads, o, lse, dO, *_blocks(dqkv, E), p=p, call_id=call_id, rng_used=used[0] if used else None,
                      q_rows=q_rows)
@@ -136,8 +136,7 @@ def attention(qkv: torch.Tensor, heads: int, p: float = 0.0, call_id: Optional[i
     if qkv.dim() != 2 or qkv.shape[1] % 3 or not kernel_applicable(qkv[:, :qkv.shape[1] // 3], heads):
         raise _lib.AgnnError(f"attention: no kernel for qkv {tuple(qkv.shape)} {qkv.dtype} with {heads} heads "
                              f"(fp32, head widths {HEAD_WIDTHS})")
-    if qkv.stride(1) != 1 or qkv.stride(0) % 4 or qkv.data_ptr() % 16:
-        qkv = qkv.contiguous()
+    qkv = _lib.rows16(qkv)
     if call_id is None:
         call_id = next(fused._CALL_IDS)
     return _AttnFn.apply(qkv, heads, float(p), int(call_id) & 0xFFFFFFFF, int(q_rows))

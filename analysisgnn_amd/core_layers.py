@@ -325,8 +325,8 @@ class _GatedAggregate(torch.autograd.Function):
     def forward(ctx, fwd: Csr, bwd: Csr, a, b, h, c):
         dev = _lib.require_gpu(a, b, h, c)
         lib = _lib.load()
-        a, b, h = a.contiguous(), b.contiguous(), h.contiguous()
-        c = c.contiguous() if c is not None else None
+        a, b, h = (_lib.rows16(t.contiguous()) for t in (a, b, h))       # dense: the kernels take ONE leading dimension for the three
+        c = _lib.rows16(c.contiguous()) if c is not None else None          # (dc is allocated like c and written with c's)
         n, H = a.shape
         out = torch.empty_like(a)
         g = _lib.Gated(fwd.rowptr.data_ptr(), fwd.col.data_ptr(), fwd.perm.data_ptr(), a.data_ptr(), b.data_ptr(),
@@ -344,7 +344,7 @@ class _GatedAggregate(torch.autograd.Function):
         c = rest[0] if ctx.has_c else None
         dev = ds.device
         lib = _lib.load()
-        ds = ds.contiguous()
+        ds = _lib.rows16(ds)
         n, H = a.shape
         da = torch.empty_like(a)
         db = torch.empty_like(b)
@@ -489,7 +489,7 @@ class _RelEdgeAggregate(torch.autograd.Function):
     def forward(ctx, fwd: Csr, bwd: Csr, h, want_d: bool):
         dev = _lib.require_gpu(h)
         lib = _lib.load()
-        h = h.contiguous()
+        h = _lib.rows16(h)
         n, F_ = h.shape
         out = torch.empty((n, 2 * F_ if want_d else F_), dtype=torch.float32, device=dev)
         _lib.check(lib.agnn_absdiff_fwd_f32(fwd.rowptr.data_ptr(), fwd.col.data_ptr(), h.data_ptr(), h.stride(0), n, F_,
@@ -505,7 +505,7 @@ class _RelEdgeAggregate(torch.autograd.Function):
         (h,) = ctx.saved_tensors
         dev = g.device
         lib = _lib.load()
-        g = g if (g.stride(1) == 1 and g.stride(0) % 4 == 0 and g.data_ptr() % 16 == 0) else g.contiguous()
+        g = _lib.rows16(g)
         n, F_ = h.shape
         dh = torch.empty_like(h)
         gs, gd = g.data_ptr(), (g.data_ptr() + 4 * F_ if ctx.want_d else None)

@@ -29,11 +29,6 @@ def advance_rng(device) -> None:
     rng_state(device)[1:2].add_(1)          # one in-place launch (indexing with [1] += 1 expands into three)
 
 
-def _al16(t: torch.Tensor) -> torch.Tensor:
-    """Parameters can be views into a flat optimizer buffer at any element offset; the kernel reads float4."""
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
 class _NormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, p, flags, call_id, seg=0, defer_ok=False, steal_refs=None, pre=None, slot_groups=None):
@@ -46,14 +41,14 @@ class _NormAct(torch.autograd.Function):
         ctx.steal_refs = leaf_refs(gamma, beta) if steal_refs is None else tuple(steal_refs)   # reshaped operands: the caller names the leaves
         ctx.slot_groups = (slot_group(gamma), slot_group(beta)) if slot_groups is None else tuple(slot_groups)
         lib = _lib.load()
-        x = x if (x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0) else x.contiguous()
+        x = _lib.rows16(x)
         n, H = x.shape
         seg = int(seg) if seg else H
         rng = rng_state(dev) if p > 0 else None
         # the (seed, step) pair this call draws from is saved with it: the live counter moves on with every training forward
         # (models.encode -> advance_rng), and backward must regenerate THIS call's masks
         used = torch.empty(2, dtype=torch.int64, device=dev) if p > 0 else None
-        gamma, beta = _al16(gamma.contiguous()), _al16(beta.contiguous())
+        gamma, beta = _lib.vec16(gamma), _lib.vec16(beta)     # (views into the flat parameter buffer lie at any element offset)
         if pre is not None:
             y, mean, rstd = pre
         else:
@@ -73,7 +68,7 @@ class _NormAct(torch.autograd.Function):
         eps, p, flags, call_id, seg = ctx.cfg
         dev = dy.device
         lib = _lib.load()
-        dy = dy if (dy.stride(1) == 1 and dy.stride(0) % 4 == 0 and dy.data_ptr() % 16 == 0) else dy.contiguous()
+        dy = _lib.rows16(dy)
         n, H = x.shape
         dx = torch.empty_like(x)
         nws = int(lib.agnn_norm_act_workspace_bytes(H))
@@ -103,10 +98,6 @@ class _NormAct(torch.autograd.Function):
         return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None
 
 
-def _ok16(t: torch.Tensor) -> bool:
-    return t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
-
-
 class _SkipAct(torch.autograd.Function):
     """z = dropout_p(relu?(x + sigmoid(skip) * (o - x)))  (agnn_skip_act_*): the HGT layer's epilogue in one launch each way."""
 
@@ -114,9 +105,9 @@ class _SkipAct(torch.autograd.Function):
     def forward(ctx, o, x, skip, relu: bool, p: float, call_id: int):
         dev = _lib.require_gpu(o)
         lib = _lib.load()
-        o = o if _ok16(o) else o.float().contiguous()
+        o = _lib.rows16(o.float())
         if x is not None:
-            x = x if _ok16(x) else x.float().contiguous()
+            x = _lib.rows16(x.float())
         n, H = o.shape
         z = torch.empty((n, H), dtype=torch.float32, device=dev)
         rng = rng_state(dev) if p > 0 else None
@@ -142,7 +133,7 @@ class _SkipAct(torch.autograd.Function):
         used = saved.pop(0) if p > 0 else None
         dev = dz.device
         lib = _lib.load()
-        dz = dz if _ok16(dz) else dz.float().contiguous()
+        dz = _lib.rows16(dz.float())
         n, H = o.shape
         do = torch.empty_like(o)
         want_dx = has_x and ctx.needs_input_grad[1]

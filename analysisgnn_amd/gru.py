@@ -105,7 +105,7 @@ class _GRULayer(torch.autograd.Function):
         if off_chain and I % 2 == 0 and all(ctx.needs_input_grad[1:5]):
             # the direction pairs' slots of the flat gradient buffer lie back to back: the products write them as the stacks
             own = grad_slot_groups(ctx.slot_groups, ((6 * Hh, I), (2, 3 * Hh, Hh), (6 * Hh,), (2, 3 * Hh)),
-                                   lambda v: all(t is not None and t.data_ptr() % 8 == 0 for t in v))
+                                   lambda v: all(t is not None and _lib.vec_ok(t, vec=2) for t in v))
         if own is not None:
             dw_ih, dw_hh, db_ih, db_hh = own
             del own

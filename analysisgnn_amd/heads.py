@@ -80,10 +80,8 @@ def heads_forward(x, W1, b1, gamma, beta, eps, W2, b2, offs, h2):
     """(z, y, mean, rstd, logits) of the whole head block in one launch (csrc/heads.hip); operands are the stacked parameters."""
     dev = _lib.require_gpu(x, W1, W2)
     with torch.no_grad():
-        xc = x.detach()
-        xc = xc if (xc.stride(1) == 1 and xc.stride(0) % 4 == 0 and xc.data_ptr() % 16 == 0) else xc.contiguous()
-        al = lambda t: t if (t.is_contiguous() and t.data_ptr() % 16 == 0) else t.contiguous().clone()     # noqa: E731
-        w1, w2 = al(W1.detach()), al(W2.detach())
+        xc = _lib.rows16(x.detach())
+        w1, w2 = _lib.vec16(W1.detach()), _lib.vec16(W2.detach())
         c = lambda t: t.detach().reshape(-1).contiguous()                                                  # noqa: E731
         T = len(offs) - 1
         N = xc.shape[0]
@@ -122,10 +120,8 @@ class _GroupedProj(torch.autograd.Function):
         ctx._wg_defer_in = all(t is None or t.is_leaf or getattr(t, "_agnn_wgrad_deferrable", False) for t in (w, b))
         ctx.steal_refs = leaf_refs(w, b)
         ctx.slot_groups = (slot_group(w), slot_group(b))         # where dw / db finally belong (linear.grad_slot_groups)
-        a = _lib.f32c(a)
-        w = _lib.f32c(w)
-        if w.data_ptr() % 16:
-            w = w.clone()
+        a = _lib.rows16(a)
+        w = _lib.rows16(w)
         G = len(offs) - 1
         sum_c = offs[-1]
         tiles = sum((offs[i + 1] - offs[i] + 31) // 32 for i in range(G))
@@ -149,7 +145,7 @@ class _GroupedProj(torch.autograd.Function):
         a, w, offs_t = ctx.saved_tensors
         G, K, tiles, sum_c, has_b = ctx.meta
         dev = a.device
-        dout = _lib.f32c(dout)
+        dout = _lib.rows16(dout, vec=1)          # [N, sum of classes]: read float by float
         N = a.shape[0]
         lib = _lib.load()
         need_w = ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2])
@@ -159,7 +155,7 @@ class _GroupedProj(torch.autograd.Function):
             own = None
             if off_chain and ctx.needs_input_grad[1] and ctx.needs_input_grad[2] == has_b and ctx.slot_groups[0]:
                 # k_gproj_dw's slab sum writes the parameters' slots of the flat gradient buffer themselves
-                own = grad_slot_groups(ctx.slot_groups, (w.shape, (sum_c,)), lambda v: v[0].data_ptr() % 8 == 0)
+                own = grad_slot_groups(ctx.slot_groups, (w.shape, (sum_c,)), lambda v: _lib.vec_ok(v[0], vec=2))
             if own is not None:
                 dw, db = own
                 del own
@@ -203,10 +199,8 @@ class _GroupedInProj(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, offs_t, offs, K):
         dev = _lib.require_gpu(x, w, offs_t)
-        x = _lib.f32c(x)
-        w = _lib.f32c(w)
-        if w.data_ptr() % 16:
-            w = w.clone()
+        x = _lib.rows16(x, vec=1)                # [N, sum of classes]: read float by float
+        w = _lib.rows16(w)
         G = len(offs) - 1
         sum_c = offs[-1]
         tiles = sum((offs[i + 1] - offs[i] + 31) // 32 for i in range(G))
@@ -225,7 +219,7 @@ class _GroupedInProj(torch.autograd.Function):
         x, w, offs_t = ctx.saved_tensors
         G, K, tiles, sum_c = ctx.meta
         dev = x.device
-        dout = _lib.f32c(dout)
+        dout = _lib.rows16(dout)
         N = x.shape[0]
         lib = _lib.load()
         dx = dw = None

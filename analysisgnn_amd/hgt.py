@@ -25,14 +25,6 @@ from .params import cat_rows, pack
 EdgeType = Tuple[str, str, str]
 
 
-def _mat(t: torch.Tensor) -> torch.Tensor:
-    if t.dtype != torch.float32 or t.dim() != 2:
-        raise _lib.AgnnError("fp32 2-D matrix expected")
-    if t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
-        t = t.contiguous()
-    return t
-
-
 class _DictLinear(nn.Module):
     """`HeteroDictLinear`: one Linear per node type, parameters under `lins.<type>`."""
 
@@ -121,7 +113,7 @@ class _HGTCore(torch.autograd.Function):
         lib = _lib.load()
         heads, D = plan.heads, plan.D
         H = heads * D
-        X = {t: _mat(x) for t, x in zip(plan.types, kqv)}
+        X = {t: _lib.rows16(x) for t, x in zip(plan.types, kqv)}
         for t, x in X.items():
             if x.shape[1] != 3 * H:
                 raise _lib.AgnnError("HGT core: kqv must be [n, 3H]")
@@ -131,8 +123,8 @@ class _HGTCore(torch.autograd.Function):
             x = X[s_t]
             N, R = x.shape[0], len(e_ids)
             ids = tuple(e * heads + h for e in e_ids for h in range(heads))
-            if ids == tuple(range(wk.shape[0])) and wk.is_contiguous() and wv.is_contiguous() and wk.data_ptr() % 16 == 0 and wv.data_ptr() % 16 == 0:
-                Wk[s_t], Wv[s_t] = wk.detach(), wv.detach()          # every relation leaves this type, in order: no gather
+            if ids == tuple(range(wk.shape[0])):
+                Wk[s_t], Wv[s_t] = _lib.vec16(wk.detach()), _lib.vec16(wv.detach())      # every relation leaves this type, in order: no gather
             else:
                 sel = _index_tensor(ids, dev)
                 Wk[s_t], Wv[s_t] = wk.detach().index_select(0, sel), wv.detach().index_select(0, sel)
@@ -238,7 +230,7 @@ class _HGTCore(torch.autograd.Function):
             if t not in stats or dm is None:                         # no incoming relation / output not used downstream: dq = 0
                 zero_q.add(t)
                 continue
-            dm = _mat(dm)
+            dm = _lib.rows16(dm)
             m, linv, out = stats[t]
             q = X[t]
             R = len(rels)

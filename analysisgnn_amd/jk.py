@@ -48,13 +48,6 @@ def kernel_applicable(module, xs) -> bool:
     return True
 
 
-def _rows16(t: torch.Tensor) -> torch.Tensor:
-    """Rows 16-byte aligned with unit column stride: the tensor itself (a row slice, a column block with its ld) or a copy."""
-    if t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16 or t.stride(0) < t.shape[1]:
-        t = t.contiguous()
-    return t
-
-
 def _params(module):
     l = module.lstm
     ps = [l.weight_ih_l0, l.weight_hh_l0, l.bias_ih_l0, l.bias_hh_l0,
@@ -70,7 +63,7 @@ def _forward(xs, P, save: bool):
     T, (M, H) = len(xs), xs[0].shape
     h = P[1].shape[1]
     nt = h // 32
-    W = [p.detach().contiguous() for p in P[:9]]
+    W = [_lib.vec16(p.detach()) for p in P[:9]]
     att_w = W[8]
     f32 = dict(dtype=torch.float32, device=dev)
     hbuf = torch.empty((2, T, M, h), **f32)          # step order: direction 1's step s is t = T - 1 - s
@@ -130,10 +123,10 @@ class _JKFn(torch.autograd.Function):
         st = _lib.stream_ptr(dev)
         M, H = xs[0].shape
         h = P[1].shape[1]
-        W = [p.detach().contiguous() for p in P]
+        W = [_lib.vec16(p.detach()) for p in P]
         att_w = W[8]
         f32 = dict(dtype=torch.float32, device=dev)
-        dout = _rows16(dout)
+        dout = _lib.rows16(dout)
         need_dx = any(ctx.needs_input_grad[1:1 + T])
         need_dp = any(ctx.needs_input_grad[1 + T:1 + T + 9])
 
@@ -225,7 +218,7 @@ def jumping_knowledge(module, xs) -> torch.Tensor:
     _lib.require_gpu(*xs, *P)
     if any(p.dtype != torch.float32 for p in P):
         raise _lib.AgnnError("jumping_knowledge: fp32 parameters expected")
-    xs = [_rows16(x) for x in xs]
+    xs = [_lib.rows16(x) for x in xs]
     if torch.is_grad_enabled() and any(t.requires_grad for t in (*xs, *P)):
         return _JKFn.apply(len(xs), *xs, *P)
     return _forward(xs, P, False)[0]

@@ -429,13 +429,9 @@ def grad_slot_groups(groups, shapes, ok=None):
 
 
 def _ok(t: torch.Tensor) -> bool:
-    return (t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 2 == 0
-            and t.shape[1] % 2 == 0 and t.data_ptr() % 8 == 0)
-
-
-def _dw_ok(dw: torch.Tensor) -> bool:
-    """A weight-gradient destination: a contiguous matrix, or a column block of one (`agnn_wgrad_item_t.ld_dw`)."""
-    return dw.dim() == 2 and dw.stride(1) == 1 and dw.stride(0) >= dw.shape[1] and dw.stride(0) % 2 == 0 and dw.data_ptr() % 8 == 0
+    """An operand of the weight-gradient kernels (float2 loads): an even width in rows the kernel can read.  A destination (a
+    contiguous matrix, or a column block of one: `agnn_wgrad_item_t.ld_dw`) is `_lib.rows_ok(dw, vec=2)`."""
+    return _lib.rows_ok(t, vec=2) and t.shape[1] % 2 == 0
 
 
 def weight_grad(dy: torch.Tensor, x: torch.Tensor, want_bias: bool, dw_out: Optional[torch.Tensor] = None,
@@ -464,7 +460,7 @@ def weight_grad(dy: torch.Tensor, x: torch.Tensor, want_bias: bool, dw_out: Opti
     lib = _lib.load()
     dev = dy.device
     if dw_out is not None:
-        if in_k != in_f or tuple(dw_out.shape) != (out_f, in_f) or not _dw_ok(dw_out) or (want_bias and (db_out is None or not db_out.is_contiguous())):
+        if in_k != in_f or tuple(dw_out.shape) != (out_f, in_f) or not _lib.rows_ok(dw_out, vec=2) or (want_bias and (db_out is None or not db_out.is_contiguous())):
             raise _lib.AgnnError("weight_grad: dw_out / db_out must be [out, in] (rows contiguous, even stride) / contiguous [out] with an even `in`")
         dw, db = dw_out, (db_out if want_bias else None)
     else:
@@ -562,8 +558,8 @@ def weight_grad_batch(items) -> None:
         n, out_f = it.dy.shape
         in_f = it.x.shape[1]
         return (BATCH and ENABLED and it.dy.is_cuda and it.dy.dim() == 2 and it.x.dim() == 2 and n >= MIN_ROWS and out_f * in_f <= MAX_OUT_IN and in_f % 2 == 0
-                and _ok(it.dy) and _ok(it.x) and it.dw_out is not None and tuple(it.dw_out.shape) == (out_f, in_f) and _dw_ok(it.dw_out)
-                and (not it.want_bias or (it.db_out is not None and it.db_out.is_contiguous() and it.db_out.data_ptr() % 8 == 0)))
+                and _ok(it.dy) and _ok(it.x) and it.dw_out is not None and tuple(it.dw_out.shape) == (out_f, in_f) and _lib.rows_ok(it.dw_out, vec=2)
+                and (not it.want_bias or (it.db_out is not None and _lib.vec_ok(it.db_out, vec=2))))
 
     def run(group):
         if len(group) == 1:
@@ -597,10 +593,8 @@ def weight_grad_batch(items) -> None:
 
 
 def _dst_ok(d: torch.Tensor, out_f: int, c0: int, c1: int) -> bool:
-    cols = c1 - c0
-    if d.dtype != torch.float32 or d.dim() != 2 or tuple(d.shape) != (out_f, cols) or d.stride(1) != 1 or d.stride(0) < cols:
-        return False
-    return d.data_ptr() % 4 == 0 if cols & 1 else (c0 % 2 == 0 and d.stride(0) % 2 == 0 and d.data_ptr() % 8 == 0)
+    cols = c1 - c0                            # an odd block is stored float by float, an even one as float2 from an even column on
+    return tuple(d.shape) == (out_f, cols) and (_lib.rows_ok(d, vec=1) if cols & 1 else (c0 % 2 == 0 and _lib.rows_ok(d, vec=2)))
 
 
 def grad_epilogue(items, sums) -> None:
@@ -617,7 +611,7 @@ def grad_epilogue(items, sums) -> None:
                 and _ok(it.dy) and _ok(it.x) and 0 < len(dsts) <= _lib.PACK_MAX_SRC and len(dbs) <= _lib.PACK_MAX_SRC
                 and all(d is not None and _dst_ok(d, out_f, c0, c1) for c0, c1, d in dsts) and bool(dbs) == it.want_bias
                 and all(d is not None and d.is_contiguous() and tuple(d.shape) == (out_f,) for d in dbs)
-                and (it.dsts is not None or all(d.data_ptr() % 8 == 0 for d in dbs)))       # (an item of the old kind: the old condition)
+                and (it.dsts is not None or all(_lib.vec_ok(d, vec=2) for d in dbs)))       # (an item of the old kind: the old condition)
 
     groups, group, products = [], [], 0
     for it in items:
@@ -675,7 +669,7 @@ def _leaf_slots(groups, out_f: int, in_f: int, odd_ok: bool = False):
 
     def ok(v):
         dw, db = v
-        return (_dw_ok(dw) or (odd_ok and dw.shape[1] & 1 and dw.stride(1) == 1)) and (db is None or db.data_ptr() % 8 == 0)
+        return (_lib.rows_ok(dw, vec=2) or (odd_ok and dw.shape[1] & 1 and dw.stride(1) == 1)) and (db is None or _lib.vec_ok(db, vec=2))
     v = grad_slot_groups(groups, ((out_f, in_f), (out_f,)), ok)
     return None if v is None else (v[0], v[1])
 
@@ -690,15 +684,14 @@ HAND_GEMM_MAX_K = 1536    # beyond it (C5's [16 000, 2 048] x [2 048, 512] layer
 
 
 def _hand_gemm_dx_ok(dy, w) -> bool:
-    return (dy.is_cuda and dy.dim() == 2 and dy.dtype == torch.float32 and w.dtype == torch.float32 and dy.shape[0] >= HAND_GEMM_MIN_ROWS
-            and w.shape[1] % 64 == 0 and w.shape[0] % 16 == 0 and dy.stride(1) == 1 and w.stride(1) == 1 and dy.stride(0) % 4 == 0
-            and w.stride(0) % 4 == 0 and dy.stride(0) >= dy.shape[1] and w.stride(0) >= w.shape[1] and dy.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
+    return (dy.is_cuda and _lib.rows_ok(dy) and _lib.rows_ok(w) and dy.shape[0] >= HAND_GEMM_MIN_ROWS
+            and w.shape[1] % 64 == 0 and w.shape[0] % 16 == 0)
 
 
 def _hand_gemm_ok(x, w, b) -> bool:
-    return (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and w.dtype == torch.float32 and x.shape[0] >= HAND_GEMM_MIN_ROWS
-            and HAND_GEMM_MIN_K <= x.shape[1] <= HAND_GEMM_MAX_K and w.shape[0] >= HAND_GEMM_MIN_N and w.shape[0] % 64 == 0 and x.shape[1] % 16 == 0 and x.stride(1) == 1 and w.stride(1) == 1 and x.stride(0) % 4 == 0
-            and w.stride(0) % 4 == 0 and x.stride(0) >= x.shape[1] and w.stride(0) >= w.shape[1] and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 and (b is None or (b.dtype == torch.float32 and b.is_contiguous())))
+    return (x.is_cuda and _lib.rows_ok(x) and _lib.rows_ok(w) and x.shape[0] >= HAND_GEMM_MIN_ROWS
+            and HAND_GEMM_MIN_K <= x.shape[1] <= HAND_GEMM_MAX_K and w.shape[0] >= HAND_GEMM_MIN_N and w.shape[0] % 64 == 0 and x.shape[1] % 16 == 0
+            and (b is None or (b.dtype == torch.float32 and b.is_contiguous())))
 
 
 def hand_gemm(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
@@ -741,6 +734,8 @@ class _LinearFn(torch.autograd.Function):
         if dy is None:
             return None, None, None, None, None
         x, w = ctx.saved_tensors
+        if dy.is_cuda and dy.dim() == 2 and dy.dtype == torch.float32 and dy.stride(1) == 1 and not _lib.rows_ok(dy, vec=1):
+            dy = _lib.rows16(dy)         # rows that overlap (the stride-0 gradient behind a row sum): no product below reads those in place
         dw = db = None
         want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
@@ -753,7 +748,7 @@ class _LinearFn(torch.autograd.Function):
             box = ctx.grad_box
             boxed = None
             if box is not None and box["uses"] == 1 and not padded and ctx.needs_input_grad[1] and want_b == bool(box["b"]):
-                boxed = grad_slots(box["leaves"], lambda v: all((_dw_ok(t) if t.dim() == 2 else t.is_contiguous()) for t in v))
+                boxed = grad_slots(box["leaves"], lambda v: all((_lib.rows_ok(t, vec=2) if t.dim() == 2 else t.is_contiguous()) for t in v))
             own = None
             if boxed is None and ctx.needs_input_grad[1] and want_b == ctx.has_bias:
                 own = _leaf_slots(ctx.slot_groups, dy.shape[1], in_f, odd_ok=padded)
@@ -836,11 +831,9 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, a
 def _hand_gemm2_ok(x0, x1, w, b) -> bool:
     """`_hand_gemm_ok` for the product on [x0 | x1]: the sizes of the concatenation, the layout of each block."""
     k0, k1 = x0.shape[1], x1.shape[1]
-    blk = lambda t: (t.is_cuda and t.dim() == 2 and t.dtype == torch.float32 and t.shape[1] % 16 == 0 and t.shape[1] > 0 and t.stride(1) == 1       # noqa: E731
-                     and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0)
-    return (blk(x0) and blk(x1) and x0.shape[0] == x1.shape[0] and x0.shape[0] >= HAND_GEMM_MIN_ROWS and w.dtype == torch.float32 and w.dim() == 2
+    blk = lambda t: t.is_cuda and _lib.rows_ok(t) and t.shape[1] % 16 == 0 and t.shape[1] > 0       # noqa: E731
+    return (blk(x0) and blk(x1) and x0.shape[0] == x1.shape[0] and x0.shape[0] >= HAND_GEMM_MIN_ROWS and _lib.rows_ok(w)
             and w.shape[1] == k0 + k1 and HAND_GEMM_MIN_K <= k0 + k1 <= HAND_GEMM_MAX_K and w.shape[0] >= HAND_GEMM_MIN_N and w.shape[0] % 64 == 0
-            and w.stride(1) == 1 and w.stride(0) % 4 == 0 and w.stride(0) >= w.shape[1] and w.data_ptr() % 16 == 0
             and (b is None or (b.dtype == torch.float32 and b.is_contiguous())))
 
 

@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .encoders import HybridGNN, MetricalGNN
-from .fused import FusedSequential, _al16, advance_rng
+from .fused import FusedSequential, advance_rng
 from .embedding import embed_cat
 from .heads import CrossTaskTransformer, fused_head_logits, fused_logit_fusion
 from .linear import Linear
@@ -60,7 +60,7 @@ class _PoolCat(torch.autograd.Function):
     @staticmethod
     def backward(ctx, du):
         inv_cnt, = ctx.saved_tensors
-        du = du if ops._view_ok(du) else _lib.f32c(du)
+        du = _lib.rows16(du)
         n, H = du.shape[0], du.shape[1] // 2
         dx = torch.empty((n, H), dtype=torch.float32, device=du.device)
         rel = _lib.make_rels([dict(src=None, rowptr=ctx.bwd.rowptr.data_ptr(), col=ctx.bwd.col.data_ptr(), ld_src=0)])
@@ -74,13 +74,13 @@ def pool_cat_norm(x: torch.Tensor, onset_edges: torch.Tensor, batch_size: int, l
     kernel's (H = 256 or 512, fp32 rows the kernel can read, at least one pooled row): the caller keeps the three launches."""
     n, H = int(x.shape[0]), int(x.shape[1])
     n_pool = min(n, int(batch_size))
-    if not (x.is_cuda and x.dim() == 2 and H in ops.ROOT_WIDTHS and n_pool >= 1 and ops._view_ok(x) and x.stride(0) >= H and ln.elementwise_affine
+    if not (x.is_cuda and x.dim() == 2 and H in ops.ROOT_WIDTHS and n_pool >= 1 and _lib.rows_ok(x) and x.stride(0) >= H and ln.elementwise_affine
             and tuple(ln.normalized_shape) == (2 * H,) and ln.weight.dtype == torch.float32):
         return None
     fwd, bwd = _onset_index(n, onset_edges, batch_size, index)
     if fwd.n_rows < n_pool or bwd.n_rows < n_pool:
         return None
-    gamma, beta = _al16(ln.weight.detach().contiguous()), _al16(ln.bias.detach().contiguous())
+    gamma, beta = _lib.vec16(ln.weight.detach()), _lib.vec16(ln.bias.detach())
     box: list = []
     u = _PoolCat.apply(x, fwd, bwd, n_pool, min(int(batch_size), n), gamma, beta, ln.eps, box)     # (sources are rows of x)
     return u, box

@@ -36,11 +36,6 @@ class AggSpec:
         return None if self.e_limit is None else self.e_limit[r]
 
 
-def _view_ok(t: torch.Tensor) -> bool:
-    return (t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0
-            and t.data_ptr() % 16 == 0)
-
-
 # When set to a list, every SpMM launch is bracketed by HIP events on the launch stream and
 # (tag, start_event, end_event, n_rel, n_rows, H, rel_stride) is appended — bench.py's live kernel timing.
 SPMM_TRACE: Optional[list] = None
@@ -90,7 +85,7 @@ class _Aggregate(torch.autograd.Function):
         H = srcs[0].shape[1]
         if H % 4 != 0:
             raise _lib.AgnnError(f"feature width {H} must be a multiple of 4 (pad with ops.pad4)")
-        srcs_c = [(_lib.f32c(s) if not _view_ok(s) else s) for s in srcs]
+        srcs_c = [_lib.rows16(s) for s in srcs]
         for s in srcs_c:
             if s.shape[1] != H:
                 raise _lib.AgnnError("all source matrices must have the same width")
@@ -98,7 +93,7 @@ class _Aggregate(torch.autograd.Function):
         n = spec.n_rows
         self_c = None
         if self_t is not None:
-            self_c = self_t if _view_ok(self_t) else _lib.f32c(self_t)
+            self_c = _lib.rows16(self_t)
             if self_c.shape[0] < n or self_c.shape[1] != H:
                 raise _lib.AgnnError("`self` must have at least n_rows rows and width H")
         if spec.root:
@@ -149,7 +144,7 @@ class _Aggregate(torch.autograd.Function):
         R = len(spec.fwd)
         n = spec.n_rows
         inv_cnt = ctx.saved_tensors[0] if spec.mean else None
-        dout = dout if _view_ok(dout) else _lib.f32c(dout)
+        dout = _lib.rows16(dout)
         dev = dout.device
         grads: List[Optional[torch.Tensor]] = []
         root_folded = False

@@ -84,12 +84,12 @@ class _SageOperands(torch.autograd.Function):
         def fan_out():
             items = []
             if G_l is not None:
-                dW_l_, db_ = _lib.f32c(dW_l), db.contiguous()
+                dW_l_, db_ = _lib.rows16(dW_l), db.contiguous()
                 for r in range(R):
                     items.append((G_l[r], [dW_l_[:, r * in_f:(r + 1) * in_f]]))
                     items.append((G_b[r].view(1, -1), [db_.view(1, -1)]))
             if G_r is not None:
-                dW_r_ = _lib.f32c(dW_r)
+                dW_r_ = _lib.rows16(dW_r)
                 for r in range(R):
                     items.append((G_r[r], [dW_r_]))
             pack(items, dev)
@@ -157,7 +157,7 @@ class _SageOperandsCat(torch.autograd.Function):
             G_l = torch.zeros((R, out_f, in_f), dtype=torch.float32, device=dev)
 
         def fan_out():
-            dW_, db_ = _lib.f32c(dW), db.contiguous()
+            dW_, db_ = _lib.rows16(dW), db.contiguous()
             items = []
             for r in range(R):
                 if r < nl:

@@ -119,7 +119,7 @@ class _LinkBCE(torch.autograd.Function):
         K = len(plans)
         dev = _lib.require_gpu(*feats)
         lib = _lib.load()
-        feats = [_lib.f32c(z) for z in feats]
+        feats = [_lib.rows16(z) for z in feats]
         H = int(feats[0].shape[1])
         for p, z in zip(plans, feats):
             if z.shape[1] != H or z.shape[0] != p.n_rows:

@@ -113,7 +113,7 @@ def row_select(q: torch.Tensor, c: torch.Tensor, q_off: Sequence[int], c_off: Se
     index) as (idx int32 [Q, ksel] of candidate positions or -1, score fp32 [Q, ksel] or +inf).  `q_rows` / `c_rows`: int32 row
     numbers of q / c per position (None: the position itself)."""
     dev = _lib.require_gpu(q, c, q_rows, c_rows)
-    q, c = _lib.f32c(q), _lib.f32c(c)
+    q, c = _lib.rows16(q), _lib.rows16(c)
     n_seg = len(q_off) - 1
     if len(c_off) != len(q_off) or n_seg < 0 or n_seg > _lib.MAX_SEG:
         raise _lib.AgnnError(f"row_select: {n_seg} segments (at most {_lib.MAX_SEG}; q_off and c_off of one length)")
@@ -172,7 +172,7 @@ class _Synthesize(torch.autograd.Function):
     def forward(ctx, x, y, cplan, rows, nbr, k, choice, gap, call_id, info):
         dev = x.device
         lib = _lib.load()
-        x = _lib.f32c(x)
+        x = _lib.rows16(x)
         N, D = x.shape
         S = int(cplan.s_off[cplan.n_seg])
         xo = torch.empty((N + S, D), dtype=torch.float32, device=dev)
@@ -201,7 +201,7 @@ class _Synthesize(torch.autograd.Function):
         cplan, k, call_id, N, D, S = ctx.cfg
         rows, nb_row, last = ctx.saved_tensors
         dev = g.device
-        g = _lib.f32c(g)
+        g = _lib.rows16(g)
         dx = g[:N].clone()
         w = torch.empty((S, D), dtype=torch.float32, device=dev)
         _lib.check(_lib.load().agnn_smote_synth_bwd_f32(g.data_ptr(), g.stride(0), N, D, _lib.C.byref(cplan), rows.data_ptr(),
@@ -257,7 +257,7 @@ class SMOTE(object):
                 raise _lib.AgnnError(f"SMOTE: neighbour choices must lie in [0, {k - 2}]")
         call_id = (next(fused._CALL_IDS) if call_id is None else int(call_id)) & 0xFFFFFFFF
         t_off = [int(cplan.t_off[i]) for i in range(cplan.n_seg + 1)]
-        xd = _lib.f32c(x.detach())
+        xd = _lib.rows16(x.detach())
         nbr, _ = row_select(xd, xd, t_off, t_off, k + 1, self._mode(), rows, rows)
         self.last_call = {}
         return _Synthesize.apply(x, y, cplan, rows, nbr, k, choice, gap, call_id, self.last_call)

@@ -38,10 +38,6 @@ def kernel_applicable(n_seq: int, T: int, heads: int, E: int, dtype, device) -> 
     return torch.device(device).type == "cuda" and dtype == torch.float32
 
 
-def _rows_ok(t: torch.Tensor, width: int) -> bool:
-    return t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= width and t.data_ptr() % 16 == 0
-
-
 def _check(who: str, qkv: torch.Tensor, T: int, heads: int) -> tuple:
     if qkv.dim() != 2 or qkv.shape[1] % 3 or T < 1 or qkv.shape[0] % T:
         raise _lib.AgnnError(f"{who}: qkv [n_seq * T, 3E] expected, got {tuple(qkv.shape)} with T = {T}")
@@ -60,7 +56,7 @@ def forward_raw(qkv: torch.Tensor, T: int, heads: int, p: float = 0.0, call_id: 
     n_seq, E = _check("task_attention.forward_raw", qkv, T, heads)
     D = E // heads
     o = torch.empty((n_seq * T, E), dtype=torch.float32, device=dev) if out is None else out
-    if tuple(o.shape) != (n_seq * T, E) or o.dtype != torch.float32 or (n_seq and not (_rows_ok(qkv, 3 * E) and _rows_ok(o, E))):
+    if tuple(o.shape) != (n_seq * T, E) or o.dtype != torch.float32 or (n_seq and not (_lib.rows_ok(qkv) and _lib.rows_ok(o))):
         raise _lib.AgnnError("task_attention.forward_raw: fp32 rows with unit column stride, 16-byte aligned, o [n_seq * T, E] expected")
     lse = torch.empty((n_seq * T, heads), dtype=torch.float32, device=dev) if want_lse else None
     rng = fused.rng_state(dev) if p > 0 else None
@@ -78,7 +74,7 @@ def backward_raw(qkv: torch.Tensor, T: int, heads: int, o: torch.Tensor, lse: to
     n_seq, E = _check("task_attention.backward_raw", qkv, T, heads)
     D = E // heads
     for name, t, w in (("o", o, E), ("dO", dO, E), ("dqkv", dqkv, 3 * E), ("qkv", qkv, 3 * E)):
-        if tuple(t.shape) != (n_seq * T, w) or t.dtype != torch.float32 or (n_seq and not _rows_ok(t, w)):
+        if tuple(t.shape) != (n_seq * T, w) or t.dtype != torch.float32 or (n_seq and not _lib.rows_ok(t)):
             raise _lib.AgnnError(f"task_attention.backward_raw: {name} must be fp32 [{n_seq * T}, {w}] with unit column stride and 16-byte aligned rows")
     if tuple(lse.shape) != (n_seq * T, heads) or lse.dtype != torch.float32 or not lse.is_contiguous():
         raise _lib.AgnnError("task_attention.backward_raw: lse must be the forward's contiguous fp32 [n_seq * T, heads]")
@@ -116,8 +112,7 @@ class _TaskAttnFn(torch.autograd.Function):
         qkv, o, lse, *used = ctx.saved_tensors
         T, heads, p, call_id = ctx.cfg
         E = o.shape[1]
-        if dO.shape[0] and not _rows_ok(dO, E):
-            dO = dO.contiguous()
+        dO = _lib.rows16(dO)
         dqkv = torch.empty_like(qkv)
         backward_raw(qkv, T, heads, o, lse, dO, dqkv, p=p, call_id=call_id, rng_used=used[0] if used else None)
         return dqkv, None, None, None, None, None
@@ -128,9 +123,8 @@ def attention(qkv: torch.Tensor, T: int, heads: int, p: float = 0.0, call_id: Op
     probabilities.  `call_id` names the dropout masks (None: the next id of the library's call-site counter; a caller that
     wants to rebuild the masks with `dropout_keep` passes its own)."""
     _lib.require_gpu(qkv)
-    _, E = _check("task_attention.attention", qkv, T, heads)
-    if qkv.shape[0] and not _rows_ok(qkv, 3 * E):
-        qkv = qkv.contiguous()
+    _check("task_attention.attention", qkv, T, heads)
+    qkv = _lib.rows16(qkv)
     if call_id is None:
         call_id = next(fused._CALL_IDS)
     need = torch.is_grad_enabled() and qkv.requires_grad          # a forward that needs no gradient writes no lse

@@ -57,6 +57,58 @@ def assert_close_rel(a, b, tol, what="", floor=1e-7):
     assert err <= tol * scale + floor, f"{what}: max abs err {err:.3e} > {tol:.1e} * max|ref| {scale:.3g}"
 
 
+class _DenseGrad(torch.autograd.Function):
+    """Identity whose backward hands on a dense, freshly allocated copy of the gradient."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.clone(memory_format=torch.contiguous_format)
+
+
+def at_offset(t, offset=1):
+    """The values of `t` as a contiguous view `offset` elements into a flat buffer (where parameters and gradient slots live)."""
+    flat = torch.zeros(t.numel() + offset, dtype=t.dtype, device=t.device)
+    v = flat[offset:].view(t.shape)
+    v.copy_(t)
+    return v
+
+
+def check_operand_layouts(fn, operands, misplaced):
+    """`fn(*operands) -> out` (float tensors, every one a leaf that takes a gradient) run three ways on the same values, the loss
+    `out.sum(0).pow(2).sum()` each time:
+      (a) dense, aligned operands, the gradient reaching `fn` as a dense copy;
+      (b) the same operands, the gradient reaching `fn` as autograd makes it: rows with strides (0, 1);
+      (c) the operands numbered in `misplaced` at element offset 1 of a flat buffer (4 bytes past a 16-byte boundary), the
+          gradient dense as in (a).
+    The kernels read the same values each time: the output and every gradient are equal bit for bit."""
+    def run(place, dense):
+        args = [place(i, t.detach()).requires_grad_(True) for i, t in enumerate(operands)]
+        out = fn(*args)
+        seen = []
+        out.register_hook(lambda g: seen.append(g.stride()))
+        (_DenseGrad.apply(out) if dense else out).sum(0).pow(2).sum().backward()
+        torch.cuda.synchronize()
+        return out.detach(), [a.grad for a in args], seen[0], args
+
+    clone = lambda i, t: t.clone()                                                    # noqa: E731
+    out_a, g_a, s_a, _ = run(clone, True)
+    out_b, g_b, s_b, _ = run(clone, False)
+    out_c, g_c, _, args_c = run(lambda i, t: at_offset(t) if i in misplaced else t.clone(), True)
+    if out_a.dim() == 2 and out_a.shape[0] > 1:
+        assert s_a == (out_a.shape[1], 1) and s_b == (0, 1), (s_a, s_b)
+    assert misplaced and all(args_c[i].data_ptr() % 16 == 4 for i in misplaced)
+    assert any(g is not None and float(g.abs().max()) > 0 for g in g_a)
+    for what, out, grads in (("broadcast gradient", out_b, g_b), ("operands at offset 1", out_c, g_c)):
+        assert torch.equal(out, out_a), f"{what}: output differs"
+        for i, (g, r) in enumerate(zip(grads, g_a)):
+            assert (g is None) == (r is None), f"{what}: gradient of operand {i}"
+            assert g is None or torch.equal(g, r), f"{what}: gradient of operand {i} differs by {float((g - r).abs().max()):.3e}"
+
+
 R3_CASES = ["r3_wrapper_hybrid_fusion", "r3_wrapper_hybrid_plain_sampled", "r3_wrapper_hybrid_jk_sum", "r3_wrapper_hgt_fusion",
             "r3_wrapper_metrical_plain", "r3_wrapper_c2_h256", "r3_wrapper_c2_h256_fusion"]
 
