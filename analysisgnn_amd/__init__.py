@@ -8,12 +8,16 @@ compute entry point raises if the HIP library or a GPU is missing.
 __version__ = "0.1.0"
 
 _PRETRAIN = ("PreEncoder", "pretrain_objective", "PretrainMetrics", "LinkPlan", "link_plan", "link_plans", "link_bce", "link_candidates")
+_EDGE_LOSS = ("EdgeDecoder", "EdgePlan", "edge_plan", "edge_consistency_loss")
 
 
 def __getattr__(name):
-    """The pretraining stage's public names (analysisgnn_amd/pretrain.py), resolved on first use: importing the package stays
-    as light as before."""
+    """The public names of the pretraining stage (analysisgnn_amd/pretrain.py) and of the edge-consistency term
+    (analysisgnn_amd/edge_loss.py), resolved on first use: importing the package stays as light as before."""
     if name in _PRETRAIN:
         from . import pretrain
         return getattr(pretrain, name)
+    if name in _EDGE_LOSS:
+        from . import edge_loss
+        return getattr(edge_loss, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -63,6 +63,11 @@ LstmCellBwd = STRUCTS["agnn_lstm_cell_bwd_t"]
 SmotePlan = STRUCTS["agnn_smote_plan_t"]
 LinkTask = STRUCTS["agnn_link_task_t"]
 LinkBwd = STRUCTS["agnn_link_bwd_t"]
+EdgeKeys = STRUCTS["agnn_edge_keys_t"]
+EdgePair = STRUCTS["agnn_edge_pair_t"]
+EdgePairBwd = STRUCTS["agnn_edge_pair_bwd_t"]
+EdgeCe = STRUCTS["agnn_edge_ce_t"]
+EdgeCeBwd = STRUCTS["agnn_edge_ce_bwd_t"]
 
 _lib: Optional[C.CDLL] = None
 

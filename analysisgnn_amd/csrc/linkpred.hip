@@ -73,22 +73,6 @@ struct LinkBwdTable {
 };
 static_assert(sizeof(LinkFwdTable) + 64 <= 4096 && sizeof(LinkBwdTable) + 64 <= 4096, "the tables travel as kernel arguments");
 
-// log2 of the lanes per candidate / row: the power of two in [4, 64] that covers H4 float4 columns (64 above 64 columns)
-inline int group_log2(int H4) {
-  int lg = 2;
-  while (lg < 6 && (1 << lg) < H4) ++lg;
-  return lg;
-}
-
-__device__ __forceinline__ float group_sum(float v, int G) {
-  for (int m = G >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-__device__ __forceinline__ int group_or(int v, int G) {
-  for (int m = G >> 1; m > 0; m >>= 1) v |= __shfl_xor(v, m);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void k_link_fwd(LinkFwdTable tab, int H4, int lg, uint32_t* __restrict__ part) {
   __shared__ float x_s[kTile];
   __shared__ int flag_s[kTile];
@@ -122,8 +106,8 @@ __global__ __launch_bounds__(256) void k_link_fwd(LinkFwdTable tab, int H4, int 
       const int32_t d32 = static_cast<int32_t>(d);
       for (int j = T.t_rowptr[s] + lig; j < r1; j += G) hit |= (T.t_col[j] == d32) ? 1 : 0;
     }
-    const float x = group_sum((a.x + a.y) + (a.z + a.w), G);
-    hit = group_or(hit, G);
+    const float x = agnn::group_sum((a.x + a.y) + (a.z + a.w), G);
+    hit = agnn::group_or(hit, G);
     if (lig == 0) {
       x_s[le] = x;
       flag_s[le] = (in ? 1 : 0) | (alive ? 2 : 0) | (hit ? 4 : 0);
@@ -323,7 +307,7 @@ extern "C" int agnn_link_bce_fwd_f32(int32_t n_tasks, const agnn_link_task_t* ta
   hipStream_t s = static_cast<hipStream_t>(stream_);
   uint32_t* part = static_cast<uint32_t*>(workspace);
   if (tiles > 0) {
-    hipLaunchKernelGGL(k_link_fwd, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, s, tab, H / 4, group_log2(H / 4), part);
+    hipLaunchKernelGGL(k_link_fwd, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, s, tab, H / 4, agnn::group_log2(H / 4), part);
     if (int rc = check_launch("link_bce_fwd")) return rc;
   }
   hipLaunchKernelGGL(k_link_final, dim3(static_cast<unsigned>(n_tasks)), dim3(256), 0, s, fin, part);
@@ -340,7 +324,7 @@ extern "C" int agnn_link_bce_bwd_f32(int32_t n_tasks, const agnn_link_bwd_t* tas
   LinkBwdTable tab;
   tab.n_tasks = n_tasks;
   tab.pad = 0;
-  const int lg = group_log2(H / 4), gpb = 256 >> lg;
+  const int lg = agnn::group_log2(H / 4), gpb = 256 >> lg;
   int64_t blocks = 0;
   for (int i = 0; i < n_tasks; ++i) {
     const agnn_link_bwd_t& t = tasks[i];

@@ -496,7 +496,8 @@ def training_loss(logits: torch.Tensor, offs: Sequence[int], labels: torch.Tenso
                   label_smoothing: float = 0.1, ignore_index: int = -1, task_params: Optional[torch.Tensor] = None,
                   ce_scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(total, per_task): the reference's training objective without its optional terms (the continual-learning ones —
-    distillation and EWC, models/analysis.py:1039-1072 — are `continual.distill` and `continual.EWC`; the edge loss is not built),
+    distillation and EWC, models/analysis.py:1039-1072 — are `continual.distill` and `continual.EWC`; the edge
+    loss is `edge_loss.edge_consistency_loss`),
         total = ce_scale * sum_t (w_t CE_t + reg_t) + lambda_feat * feat.pow(2).mean(),     ce_scale = 1 / T by default
     (models/analysis.py:1034-1036 `loss_dict.pop("total") / len(labels_dict)`, :984, :1072); with `task_params` (the `params`
     of `MultiTaskLoss`, --mt_strategy wloss) w_t = 0.5 / p_t^2 and reg_t = log(1 + p_t^2) (models/chord.py:39-49), otherwise

@@ -24,7 +24,8 @@ Departures from the reference, both deliberate:
   not depend on their order.  Logits and labels come back in the order of `cat(onset, consecutive)`.
 
 Out of scope: `FAMO` (the reference's own call `FAMO(n_tasks=4, ...)` does not match its constructor, SURVEY A.7: the effective
-objective is the plain sum built here), the Lightning optimizer plumbing, `EdgeDecoder`."""
+objective is the plain sum built here), the Lightning optimizer plumbing.  (`EdgeDecoder`, which reuses the per-edge machinery
+here, is `analysisgnn_amd/edge_loss.py`.)"""
 from __future__ import annotations
 
 from dataclasses import dataclass, field

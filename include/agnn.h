@@ -38,6 +38,8 @@
  *   agnn_taskattn_*       `CrossTaskTransformer`: attention over the task tokens of every note (ref: models/analysis.py:408-418)
  *   agnn_link_bce_*       the staff / voice link prediction of the pretraining stage: endpoint gathers, dot product,
  *                         BCEWithLogitsLoss, pair membership and the index_add_ backward (ref: models/analysis.py:397-401, :704-731)
+ *   agnn_edge_*           `EdgeDecoder` and the edge-consistency term of the continual trainer: pair features with in-kernel
+ *                         dropout, edge labels, the two-class cross entropy (ref: models/analysis.py:805-836, :986-1019)
  *
  * Conventions (all entry points)
  *   - plain pointers and sizes only; every `const T*`/`T*` marked (device) is device memory owned
@@ -1148,6 +1150,114 @@ size_t agnn_link_bce_workspace_bytes(int32_t n_tasks, const agnn_link_task_t* ta
 int agnn_link_bce_fwd_f32(int32_t n_tasks, const agnn_link_task_t* tasks, int32_t H, void* workspace, size_t workspace_bytes,
                           agnn_stream_t stream);
 int agnn_link_bce_bwd_f32(int32_t n_tasks, const agnn_link_bwd_t* tasks, int32_t H, const float* scale, agnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Edge-consistency term of the continual trainer (ref: models/analysis.py:805-836 `EdgeDecoder`, :986-1019; csrc/edgedec.hip):
+ * for every note-note relation r the selected edges e = (s, d) are classified "all label rows agree at s and d" from the product
+ * of the two ends' embeddings.  `embed[r]` is row-wise up to its dropout, so A_r = LN(ReLU(x W_r^T + b_r)) is computed once per
+ * node (a column block of a stacked [n, R H] matrix, its own leading dimension) and the dropout is applied per (edge, end, column)
+ * inside the pair kernel.  One call serves a table (HOST, read during the call) of at most AGNN_MAX_SEG relations; H is shared.
+ * H % 4 == 0, 4 <= H <= 512, rows 16-byte aligned, leading dimensions multiples of 4 floats: AGNN_EINVAL / AGNN_EALIGN before
+ * any HIP call otherwise, as for NULL pointers, negative sizes and limit > n.  No float atomics; two runs give the same bits.
+ * An edge is ALIVE when 0 <= src, dst < limit (limit <= n; an unselected edge carries ids outside that range: edge_loss.edge_plan).
+ * `pos0` is the global position of the relation's first edge: the masks are indexed by pos0 + e.
+ *
+ * agnn_edge_select_keys:  key[e] = (word << 31) | e for an alive edge, word = the first word of the random stream at index
+ *   pos0 + e (E < 2^31: the keys of a relation are distinct), INT64_MAX otherwise: the k smallest keys are a uniform k-subset.
+ * agnn_edge_pair_fwd_f32:  f[e, :] = m1 * a[src, :] * m2 * a[dst, :], m1 / m2 keep factors 0 or 1 / (1 - p) of end 0 / 1:
+ *   columns 4 q .. 4 q + 3 take the four words of the stream at index ((pos0 + e) 2 + end) (H / 4) + q.  p == 0: no bits are
+ *   drawn, rng_state may be NULL.  label[e] = 1 iff labels[k, src] == labels[k, dst] for all K rows of `labels` (int64 [K, >=
+ *   limit], row stride ld_labels; equal -1s are equal; labels == NULL or K == 0: label 0).  An edge that is not alive reads no
+ *   row: f row zero, label 0.  With p > 0 the (seed, step) read is copied to rng_used (device int64[2]) for the backward.
+ * agnn_edge_pair_bwd_f32:  da[i, :] = sum_{e: src_e = i} df[e] * m1 m2 * a[dst_e] + sum_{e: dst_e = i} df[e] * m1 m2 * a[src_e]
+ *   for every row i < n, from the edge list's CSR by source (s_*: col = destination) and by destination (d_*: col = source),
+ *   perm = the edge's position (agnn_csr_build).  Every row of da is written exactly once (rows without an alive edge: zeros); a
+ *   self loop lies in both CSRs and contributes twice.  Entries whose col or perm is out of range, and rows >= limit, add nothing.
+ * agnn_edge_ce_fwd_f32:  per alive edge the two logits y[e] . w4[c] + b4[c] (w4 [2, H] dense, 16-byte aligned), the
+ *   label-smoothed two-class cross entropy  -sum_c q_c log softmax_c, q = (1 - smoothing) onehot(label) + smoothing / 2, and its
+ *   finished coefficient dlogit[e, c] = softmax_c - q_c; edges that are not alive read no row and get logits 0, dlogit 0.  Per
+ *   relation: loss[0] = sum / alive count, inv_cnt[0] = 1 / alive count, counts[5] = alive, tp, fp, fn, tn with "predicted
+ *   positive" = logit 1 > logit 0; a relation without an alive edge gets loss 0 and inv_cnt 0 (torch: NaN).  total[0] = (sum of
+ *   the relations' losses) / n_rel.  The loss is summed per tile of 64 edges into the workspace (agnn_edge_ce_workspace_bytes)
+ *   and the tiles by a second kernel, both in a fixed order.
+ * agnn_edge_ce_bwd_f32:  dy[e, :] = scale[r] (dlogit[e, 0] w4[0, :] + dlogit[e, 1] w4[1, :]) for every edge (zeros where not
+ *   alive), dw4[c, :] = sum_e scale[r] dlogit[e, c] y[e, :], db4[c] = sum_e scale[r] dlogit[e, c] as fixed-order partials in the
+ *   workspace (agnn_edge_ce_bwd_workspace_bytes) plus one reduction.  scale: (device) one float per relation.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const int64_t* src;      /* (device) [E] */
+  const int64_t* dst;      /* (device) [E] */
+  int64_t E;
+  int64_t limit;
+  int64_t pos0;
+  int64_t* key;            /* (device) [E] */
+} agnn_edge_keys_t;
+typedef struct {
+  const float* a;          /* (device) [n, H], row stride ld_a */
+  int64_t ld_a;
+  int64_t n;
+  const int64_t* src;      /* (device) [E] */
+  const int64_t* dst;      /* (device) [E] */
+  int64_t E;
+  int64_t limit;
+  int64_t pos0;
+  float* f;                /* (device) [E, H], row stride ld_f */
+  int64_t ld_f;
+  uint8_t* label;          /* (device) [E] */
+} agnn_edge_pair_t;
+typedef struct {
+  const float* a;          /* (device) [n, H], row stride ld_a */
+  int64_t ld_a;
+  int64_t n;
+  const float* df;         /* (device) [E, H], row stride ld_df */
+  int64_t ld_df;
+  int64_t E;
+  int64_t limit;
+  int64_t pos0;
+  const int32_t* s_rowptr; /* (device) [n + 1] */
+  const int32_t* s_col;
+  const int32_t* s_perm;
+  const int32_t* d_rowptr; /* (device) [n + 1] */
+  const int32_t* d_col;
+  const int32_t* d_perm;
+  float* da;               /* (device) [n, H], row stride ld_da */
+  int64_t ld_da;
+} agnn_edge_pair_bwd_t;
+typedef struct {
+  const float* y;          /* (device) [E, H], row stride ld_y */
+  int64_t ld_y;
+  const int64_t* src;      /* (device) [E] */
+  const int64_t* dst;      /* (device) [E] */
+  const uint8_t* label;    /* (device) [E] */
+  int64_t E;
+  int64_t limit;
+  float* logit;            /* (device) [E, 2] */
+  float* dlogit;           /* (device) [E, 2] */
+  float* loss;             /* (device) [1] */
+  float* inv_cnt;          /* (device) [1] */
+  int32_t* counts;         /* (device) [5] */
+} agnn_edge_ce_t;
+typedef struct {
+  const float* y;          /* (device) [E, H], row stride ld_y */
+  int64_t ld_y;
+  const float* dlogit;     /* (device) [E, 2] */
+  int64_t E;
+  float* dy;               /* (device) [E, H], row stride ld_dy */
+  int64_t ld_dy;
+} agnn_edge_ce_bwd_t;
+int agnn_edge_select_keys(int32_t n_rel, const agnn_edge_keys_t* rels, const int64_t* rng_state, uint32_t call_id,
+                          agnn_stream_t stream);
+int agnn_edge_pair_fwd_f32(int32_t n_rel, const agnn_edge_pair_t* rels, int32_t H, const int64_t* labels, int32_t K,
+                           int64_t ld_labels, float p, const int64_t* rng_state, uint32_t call_id, int64_t* rng_used,
+                           agnn_stream_t stream);
+int agnn_edge_pair_bwd_f32(int32_t n_rel, const agnn_edge_pair_bwd_t* rels, int32_t H, float p, const int64_t* rng_state,
+                           uint32_t call_id, agnn_stream_t stream);
+size_t agnn_edge_ce_workspace_bytes(int32_t n_rel, const agnn_edge_ce_t* rels);
+int agnn_edge_ce_fwd_f32(int32_t n_rel, const agnn_edge_ce_t* rels, int32_t H, const float* w4, const float* b4, float smoothing,
+                         float* total, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+size_t agnn_edge_ce_bwd_workspace_bytes(int32_t n_rel, const agnn_edge_ce_bwd_t* rels, int32_t H);
+int agnn_edge_ce_bwd_f32(int32_t n_rel, const agnn_edge_ce_bwd_t* rels, int32_t H, const float* w4, const float* scale,
+                         float* dw4, float* db4, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
 
 #ifdef __cplusplus
 }
