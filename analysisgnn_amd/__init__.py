@@ -9,15 +9,20 @@ __version__ = "0.1.0"
 
 _PRETRAIN = ("PreEncoder", "pretrain_objective", "PretrainMetrics", "LinkPlan", "link_plan", "link_plans", "link_bce", "link_candidates")
 _EDGE_LOSS = ("EdgeDecoder", "EdgePlan", "edge_plan", "edge_consistency_loss")
+_SCORE_GRAPH = ("DeviceScoreGraph", "build_score_graph", "sort_notes")
 
 
 def __getattr__(name):
-    """The public names of the pretraining stage (analysisgnn_amd/pretrain.py) and of the edge-consistency term
-    (analysisgnn_amd/edge_loss.py), resolved on first use: importing the package stays as light as before."""
+    """The public names of the pretraining stage (analysisgnn_amd/pretrain.py), of the edge-consistency term
+    (analysisgnn_amd/edge_loss.py) and of score graph construction (analysisgnn_amd/score_graph.py), resolved on first use: importing
+    the package stays as light as before."""
     if name in _PRETRAIN:
         from . import pretrain
         return getattr(pretrain, name)
     if name in _EDGE_LOSS:
         from . import edge_loss
         return getattr(edge_loss, name)
+    if name in _SCORE_GRAPH:
+        from . import score_graph
+        return getattr(score_graph, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

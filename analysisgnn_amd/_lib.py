@@ -68,6 +68,8 @@ EdgePair = STRUCTS["agnn_edge_pair_t"]
 EdgePairBwd = STRUCTS["agnn_edge_pair_bwd_t"]
 EdgeCe = STRUCTS["agnn_edge_ce_t"]
 EdgeCeBwd = STRUCTS["agnn_edge_ce_bwd_t"]
+ScoreGraphArgs = STRUCTS["agnn_score_graph_t"]
+ScoreGroupsArgs = STRUCTS["agnn_score_groups_t"]
 
 _lib: Optional[C.CDLL] = None
 

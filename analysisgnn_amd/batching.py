@@ -37,18 +37,7 @@ class ScoreStore:
         sizes = [int(g.num_nodes["note"]) for g in graphs]
         self.score_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         n = int(self.score_start[-1])
-        self.num_notes = n
-        gen = torch.Generator().manual_seed(seed)
-        width = (in_channels + 3) & ~3                       # feature rows padded to 16 bytes (zero spare columns)
-        x = torch.zeros(n, width)
-        x[:, :in_channels] = torch.randn(n, in_channels, generator=gen)
-        self.in_channels = in_channels
-        self.x = x.to(dev)
-        attrs = [torch.randint(0, 35, (n,), generator=gen), torch.randint(0, 15, (n,), generator=gen)]
-        self.tasks = dict(tasks) if tasks else {}
-        for c in self.tasks.values():
-            attrs.append(torch.randint(0, c, (n,), generator=gen))
-        self.attrs = torch.stack(attrs).to(dev)              # int64 [2 + T, n]: pitch spelling, key signature, labels
+        gen = self._note_features(n, in_channels, tasks, seed)
         self.onset_div = torch.from_numpy(np.concatenate([g.onset_div for g in graphs])).to(dev)
         specs, self._keep = [], []
         for et in self.edge_types:
@@ -71,9 +60,55 @@ class ScoreStore:
                 ids.append(e[1] + off)
                 off += int(g.num_nodes[t])
             self.group_of[t] = torch.from_numpy(np.concatenate(ids).astype(np.int32)).to(dev)
-            xg = torch.zeros(off, width)
-            xg[:, :in_channels] = torch.randn(off, in_channels, generator=gen)
-            self.group_x[t] = xg.to(dev)
+            self._group_features(t, off, gen)
+
+    def _note_features(self, n: int, in_channels: int, tasks: Optional[Dict[str, int]], seed: int) -> torch.Generator:
+        """Synthetic (seeded) features, spellings, keys and labels of `n` notes; returns the generator for the groups' features."""
+        self.num_notes = n
+        gen = torch.Generator().manual_seed(seed)
+        width = (in_channels + 3) & ~3                       # feature rows padded to 16 bytes (zero spare columns)
+        x = torch.zeros(n, width)
+        x[:, :in_channels] = torch.randn(n, in_channels, generator=gen)
+        self.in_channels = in_channels
+        self.x = x.to(self.device)
+        attrs = [torch.randint(0, 35, (n,), generator=gen), torch.randint(0, 15, (n,), generator=gen)]
+        self.tasks = dict(tasks) if tasks else {}
+        for c in self.tasks.values():
+            attrs.append(torch.randint(0, c, (n,), generator=gen))
+        self.attrs = torch.stack(attrs).to(self.device)      # int64 [2 + T, n]: pitch spelling, key signature, labels
+        return gen
+
+    def _group_features(self, t: str, n_groups: int, gen: torch.Generator) -> None:
+        xg = torch.zeros(n_groups, self.x.shape[1])
+        xg[:, :self.in_channels] = torch.randn(n_groups, self.in_channels, generator=gen)
+        self.group_x[t] = xg.to(self.device)
+
+    @classmethod
+    def from_notes(cls, onset_div, duration_div, score_start, in_channels: int, device, tasks: Optional[Dict[str, int]] = None,
+                   seed: int = 0, *, add_beats: bool = False, add_measures: bool = False, reverse_note_edges: bool = False) -> "ScoreStore":
+        """The store of the scores whose note arrays are concatenated in `onset_div` / `duration_div` (int64; numpy or tensors)
+        with `score_start` (host, S + 1 offsets): the graphs come from `score_graph.build_score_graph` on the device — no numpy
+        graphs, no host copies of edges.  Same relations, same CSRs, same seeded features as `ScoreStore(graphs, ...)` over
+        `synth` graphs of the same notes."""
+        from .score_graph import build_score_graph
+        self = cls.__new__(cls)
+        dev = torch.device(device)
+        self.device = dev
+        on, du = (torch.as_tensor(v, dtype=torch.int64).to(dev) for v in (onset_div, duration_div))
+        g = build_score_graph(on, du, score_start, add_beats=add_beats, add_measures=add_measures, reverse_note_edges=reverse_note_edges)
+        self.edge_types = [et for et in g.edge_index_dict if et[0] == "note" and et[2] == "note"]
+        self.score_start = np.asarray(score_start, dtype=np.int64)
+        n = int(on.numel())
+        gen = self._note_features(n, in_channels, tasks, seed)
+        self.onset_div = g.onset_div
+        self._keep = [g.edge_index_dict[et] for et in self.edge_types]
+        self.csr = build_csr([SegSpec(row=e[1], col=e[0], n_rows=n) for e in self._keep])
+        self.group_types = [t for t in ("beat", "measure") if ("note", "connects", t) in g.edge_index_dict]
+        self.group_of, self.group_x = {}, {}
+        for t in self.group_types:
+            self.group_of[t] = g.edge_index_dict[("note", "connects", t)][1].to(torch.int32)
+            self._group_features(t, g.num_nodes[t], gen)
+        return self
 
     def random_windows(self, n_sub: int, n_targets: int, rng: np.random.Generator) -> np.ndarray:
         """What the loader's sampler decides on the host: `n_sub` (score, first target) pairs -> global ids, int32."""

@@ -6,7 +6,8 @@ predict pipeline can switch imports:
     where the predicted class changes.  The scatter runs on the gather-reduce kernel (all four RNA keys in ONE launch);
     the per-change-point Python loop of the reference (:96-100) is one vectorised assignment.
   * `predict` — what `ContinualAnalysisGNN.predict` does after graph construction (models/analysis.py:1533-1588):
-    eval-mode forward with `neighbor_mask_* = None`, softmax, onset-wise aggregation.
+    eval-mode forward with `neighbor_mask_* = None`, softmax, onset-wise aggregation.  `predict_from_notes` starts one step
+    earlier, at the note array: the graph is built on the device (score_graph.py).
   * `checkpoint_state_dict` / `load_reference_checkpoint` — a Lightning `.ckpt` of the reference
     (inference/predict_analysis.py:150-159: `ContinualAnalysisGNN.load_from_checkpoint`) -> this build's `state_dict`.
     Read with `torch.load(weights_only=True)` only.
@@ -131,6 +132,30 @@ def predict(model, pitch_spelling, key_signature, x_dict, edge_index_dict, batch
                                            onset_div=onset_div)
     finally:
         model.train(was)
+
+
+def predict_from_notes(model, pitch_spelling, key_signature, x_note, onset_div, duration_div, *, x_beat=None, x_measure=None,
+                       tasks: Optional[Iterable[str]] = None, score_start=None) -> Dict[str, torch.Tensor]:
+    """`ContinualAnalysisGNN.predict` from the note array on (models/analysis.py:1527-1588): the score graph is built on the
+    device (`score_graph.build_score_graph`, in the place of graphmuse's `create_score_graph`, :1535) with the node and edge types
+    the model's encoder was constructed with, then `predict` runs as it is.  The notes are in (onset, pitch) order
+    (`score_graph.sort_notes`); `x_beat` / `x_measure` carry one row per beat / measure when the model has those node types;
+    `score_start` (host) delimits several scores."""
+    from .score_graph import build_score_graph
+    node_types, edge_types = model.encoder.metadata
+    g = build_score_graph(onset_div, duration_div, score_start,
+                          add_beats="beat" in node_types, add_measures="measure" in node_types,
+                          reverse_note_edges=("note", "consecutive_rev", "note") in edge_types,
+                          reverse_metrical_edges=any(et[1] == "rev_connects" for et in edge_types))
+    if list(g.num_nodes) != list(node_types) or list(g.edge_index_dict) != [tuple(et) for et in edge_types]:
+        raise _lib.AgnnError(f"the model's metadata {node_types}, {edge_types} is not a score graph's: {g.metadata()}")
+    x_dict = {"note": x_note}
+    for t, x in (("beat", x_beat), ("measure", x_measure)):
+        if t in g.num_nodes:
+            if x is None or int(x.shape[0]) != g.num_nodes[t]:
+                raise _lib.AgnnError(f"x_{t}: {g.num_nodes[t]} rows needed (one per {t}), got {None if x is None else tuple(x.shape)}")
+            x_dict[t] = x
+    return predict(model, pitch_spelling, key_signature, x_dict, g.edge_index_dict, g.batch_dict, onset_div=g.onset_div, tasks=tasks)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -1259,6 +1259,82 @@ size_t agnn_edge_ce_bwd_workspace_bytes(int32_t n_rel, const agnn_edge_ce_bwd_t*
 int agnn_edge_ce_bwd_f32(int32_t n_rel, const agnn_edge_ce_bwd_t* rels, int32_t H, const float* w4, const float* scale,
                          float* dw4, float* db4, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Score graph construction (ref: utils/hgraph.py:214-300 `hetero_graph_from_note_array`; csrc/scoregraph.hip): the note arrays of
+ * one or many scores, concatenated on the device — onset_div / duration_div int64 [n_notes], score_start int32 [n_scores + 1] —
+ * become the four note relations as int64 COO with GLOBAL note ids.  Inside a score onsets are non-decreasing, and
+ * 0 <= onset, 0 <= duration, onset + duration < 2^31.  With end = onset + duration and lb / ub the lower / upper bound inside the
+ * score's slice, source i reaches
+ *   relation 0 onset        [lb(onset_i), ub(onset_i)), i itself only with AGNN_SG_SELF_LOOPS
+ *   relation 1 consecutive  [lb(end_i), ub(end_i))
+ *   relation 2 during       [ub(onset_i), max(ub(onset_i), lb(end_i)))
+ *   relation 3 rest         when no note of the score starts at end_i and a later onset exists: the onset group of the first one
+ * Edges are source-major with destinations ascending; rest takes its sources in stable order of end: (end, source, destination).
+ * edges[r] is int64 [2, cap[r]] (row 0 sources, row 1 destinations), or [3, cap[r]] when bit r of rev_mask is set: row 2 repeats
+ * row 0, so that rows 1 .. 2 are the reverse relation without a copy.  Slots past the real count hold -1 (what agnn_csr_build
+ * drops).  totals (device int64[4]) receives the real counts, note_score (device int64[n_notes], may be NULL) every note's score.
+ * faults (device int32[AGNN_SG_FAULT_WORDS], caller-owned, zeroed by the caller, only ever incremented) COUNTS bad input, one word
+ * per kind: an onset that decreases inside a score, a value outside the range above, a score_start that does not tile
+ * [0, n_notes), per relation an edge count over its capacity, more groups than capacity (agnn_score_groups).  A score with a
+ * fault gets no edge, a bad score_start leaves every score without edges, an overflowing relation is cut at its capacity; nothing
+ * is written out of range in any of these cases and the agnn_check_status word is not involved.
+ * agnn_score_graph_count does everything up to the totals and leaves the runs in the workspace; agnn_score_graph_fill writes the
+ * edges from that workspace (same g apart from edges / cap / rev_mask); agnn_score_graph_build is both.  Stream-ordered, no host
+ * read.  n_scores < 1, n_notes < 1, NULL pointers, negative capacities: AGNN_EINVAL; a workspace below
+ * agnn_score_graph_workspace_bytes: AGNN_ENOMEM.
+ *
+ * agnn_score_groups: metrical nodes.  key (int64 [n_notes], taken as floor(key / div), non-decreasing inside a score) -> a compact
+ * group id per note, global over the scores: a note opens a group when it starts a score or its key differs from its
+ * predecessor's.  note_edge int64 [2 (3 with rev), n_notes] = (note, group); per group < cap its score, its first note and, with
+ * parent_edge (int64 [2 (3 with rev), cap]), the pair (group, parent_of[first note]) — beat -> measure with parent_of = row 1 of
+ * the measures' note_edge; padding groups hold -1.  per_score (int64 [n_scores]) and total (int64 [1]) receive the group counts.
+ * A decreasing key is counted in faults[AGNN_SG_FAULT_ORDER] (it still only opens a group).
+ * ------------------------------------------------------------------------------------------ */
+#define AGNN_SG_SELF_LOOPS     1u
+#define AGNN_SG_FAULT_ORDER    0
+#define AGNN_SG_FAULT_RANGE    1
+#define AGNN_SG_FAULT_SCORES   2
+#define AGNN_SG_FAULT_OVERFLOW 3   /* + relation: words 3 .. 6 */
+#define AGNN_SG_FAULT_GROUPS   7
+#define AGNN_SG_FAULT_WORDS    8
+typedef struct {
+  const int64_t* onset_div;      /* (device) [n_notes] */
+  const int64_t* duration_div;   /* (device) [n_notes] */
+  const int32_t* score_start;    /* (device) [n_scores + 1] */
+  int64_t n_notes;
+  int32_t n_scores;
+  uint32_t flags;                /* AGNN_SG_SELF_LOOPS */
+  uint32_t rev_mask;
+  int64_t* edges[4];             /* (device) out int64 [2 or 3, cap[r]] */
+  int64_t cap[4];
+  int64_t* totals;               /* (device) out int64[4] */
+  int64_t* note_score;           /* (device) out int64[n_notes] or NULL */
+  int32_t* faults;               /* (device) int32[AGNN_SG_FAULT_WORDS] */
+} agnn_score_graph_t;
+typedef struct {
+  const int64_t* key;            /* (device) [n_notes] */
+  int64_t div;
+  const int32_t* score_start;    /* (device) [n_scores + 1] */
+  int64_t n_notes;
+  int32_t n_scores;
+  int32_t rev;
+  const int64_t* parent_of;      /* (device) [n_notes] or NULL */
+  int64_t* note_edge;            /* (device) out int64 [2 or 3, n_notes] */
+  int64_t cap;
+  int64_t* group_score;          /* (device) out int64[cap] or NULL */
+  int64_t* group_first;          /* (device) out int64[cap] or NULL */
+  int64_t* parent_edge;          /* (device) out int64 [2 or 3, cap] or NULL */
+  int64_t* per_score;            /* (device) out int64[n_scores] or NULL */
+  int64_t* total;                /* (device) out int64[1] or NULL */
+  int32_t* faults;               /* (device) int32[AGNN_SG_FAULT_WORDS] */
+} agnn_score_groups_t;
+size_t agnn_score_graph_workspace_bytes(int64_t n_notes, int32_t n_scores);
+int agnn_score_graph_count(const agnn_score_graph_t* g /* (host) */, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+int agnn_score_graph_fill(const agnn_score_graph_t* g /* (host) */, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+int agnn_score_graph_build(const agnn_score_graph_t* g /* (host) */, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+size_t agnn_score_groups_workspace_bytes(int64_t n_notes);
+int agnn_score_groups(const agnn_score_groups_t* g /* (host) */, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
