@@ -10,12 +10,13 @@ __version__ = "0.1.0"
 _PRETRAIN = ("PreEncoder", "pretrain_objective", "PretrainMetrics", "LinkPlan", "link_plan", "link_plans", "link_bce", "link_candidates")
 _EDGE_LOSS = ("EdgeDecoder", "EdgePlan", "edge_plan", "edge_consistency_loss")
 _SCORE_GRAPH = ("DeviceScoreGraph", "build_score_graph", "sort_notes")
+_DESCRIPTORS = ("note_features", "VOICE_FEATURES", "CADENCE_FEATURES")
 
 
 def __getattr__(name):
     """The public names of the pretraining stage (analysisgnn_amd/pretrain.py), of the edge-consistency term
-    (analysisgnn_amd/edge_loss.py) and of score graph construction (analysisgnn_amd/score_graph.py), resolved on first use: importing
-    the package stays as light as before."""
+    (analysisgnn_amd/edge_loss.py), of score graph construction (analysisgnn_amd/score_graph.py) and of the note descriptors
+    (analysisgnn_amd/descriptors.py), resolved on first use: importing the package stays as light as before."""
     if name in _PRETRAIN:
         from . import pretrain
         return getattr(pretrain, name)
@@ -25,4 +26,7 @@ def __getattr__(name):
     if name in _SCORE_GRAPH:
         from . import score_graph
         return getattr(score_graph, name)
+    if name in _DESCRIPTORS:
+        from . import descriptors
+        return getattr(descriptors, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

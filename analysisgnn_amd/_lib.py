@@ -70,6 +70,7 @@ EdgeCe = STRUCTS["agnn_edge_ce_t"]
 EdgeCeBwd = STRUCTS["agnn_edge_ce_bwd_t"]
 ScoreGraphArgs = STRUCTS["agnn_score_graph_t"]
 ScoreGroupsArgs = STRUCTS["agnn_score_groups_t"]
+NoteFeaturesArgs = STRUCTS["agnn_note_features_t"]
 
 _lib: Optional[C.CDLL] = None
 

@@ -135,13 +135,21 @@ def predict(model, pitch_spelling, key_signature, x_dict, edge_index_dict, batch
 
 
 def predict_from_notes(model, pitch_spelling, key_signature, x_note, onset_div, duration_div, *, x_beat=None, x_measure=None,
-                       tasks: Optional[Iterable[str]] = None, score_start=None) -> Dict[str, torch.Tensor]:
+                       tasks: Optional[Iterable[str]] = None, score_start=None, note_fields=None,
+                       feature_type: str = "voice") -> Dict[str, torch.Tensor]:
     """`ContinualAnalysisGNN.predict` from the note array on (models/analysis.py:1527-1588): the score graph is built on the
     device (`score_graph.build_score_graph`, in the place of graphmuse's `create_score_graph`, :1535) with the node and edge types
     the model's encoder was constructed with, then `predict` runs as it is.  The notes are in (onset, pitch) order
     (`score_graph.sort_notes`); `x_beat` / `x_measure` carry one row per beat / measure when the model has those node types;
-    `score_start` (host) delimits several scores."""
+    `score_start` (host) delimits several scores.  With `x_note=None` and `note_fields` (the note array's fields as device tensors)
+    the note rows are computed on the device too: `descriptors.note_features(note_fields, feature_type, score_start)`, the
+    reference's `select_features` (:1531)."""
     from .score_graph import build_score_graph
+    if x_note is None:
+        if note_fields is None:
+            raise _lib.AgnnError("predict_from_notes needs x_note, or note_fields to compute it from")
+        from .descriptors import note_features
+        x_note = note_features(note_fields, feature_type, score_start)
     node_types, edge_types = model.encoder.metadata
     g = build_score_graph(onset_div, duration_div, score_start,
                           add_beats="beat" in node_types, add_measures="measure" in node_types,

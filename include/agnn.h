@@ -1335,6 +1335,59 @@ int agnn_score_graph_build(const agnn_score_graph_t* g /* (host) */, void* works
 size_t agnn_score_groups_workspace_bytes(int64_t n_notes);
 int agnn_score_groups(const agnn_score_groups_t* g /* (host) */, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Note descriptors (ref: descriptors/general.py:110-139 `select_features`, descriptors/utils/note_features.py:176-226
+ * `get_voice_separation_features`, descriptors/utils/cadence_features.py:6-119 `get_cad_features`; csrc/notefeat.hip): the note
+ * array of one or many scores, concatenated on the device, becomes x (fp32 [n_notes, 25 | 56], row stride ld_x), the rows that
+ * `in_channels` counts.  Inside a score the notes are in (onset, pitch) order, as for agnn_score_graph_*, and onset_beat does not
+ * decrease where onset_div does not; nothing is reordered.
+ *   AGNN_NF_VOICE    25 columns: 1 - tanh(duration_beat / ts_beats); remainder(onset_beat, ts_beats) / ts_beats (the remainder
+ *                    has the divisor's sign); remainder(onset_beat, 1) == 0; one-hot of pitch % 12; one-hot of pitch / 12 (10)
+ *   AGNN_NF_CADENCE  those 25, then the 31 columns of get_cad_features(include_pitch_spelling=False), in its order (DESIGN.md,
+ *                    "Note descriptors").  Needs voice and is_downbeat; a non-zero is_downbeat is written as 1.
+ * is_note_onset may be NULL (all ones), as the reference appends the field when it is absent.
+ * faults (device int32[AGNN_NF_FAULT_WORDS], caller-owned, zeroed by the caller, only ever incremented) COUNTS bad input, one
+ * word per kind and one count per offending note: pitch outside [0, 120) (the reference raises), ts_beats <= 0, voice outside
+ * [0, 2^15) (where voice is given), an onset_div below its predecessor's inside a score; and ONE count when score_start does not
+ * tile [0, n_notes).  An offending note's row is zeros and the note is left out of every chord, window and voice list, so the
+ * other rows are those of the array without it (where what is left is in onset order; otherwise they are unspecified).  A bad
+ * score_start zeroes every row.  No read leaves the score's slice and no write leaves x's rows in any of these cases; the
+ * agnn_check_status word is not involved.
+ * Stream-ordered, no host read, no allocation, integer atomics only (bitwise reproducible), capturable.  n_notes < 1,
+ * n_scores < 1, NULL pointers, ld_x below the set's width, an unknown feature_set: AGNN_EINVAL before any HIP call; a workspace
+ * below agnn_note_features_workspace_bytes: AGNN_ENOMEM.
+ * ------------------------------------------------------------------------------------------ */
+#define AGNN_NF_VOICE          0
+#define AGNN_NF_CADENCE        1
+#define AGNN_NF_VOICE_WIDTH    25
+#define AGNN_NF_CADENCE_WIDTH  56
+#define AGNN_NF_FAULT_PITCH    0
+#define AGNN_NF_FAULT_TS       1
+#define AGNN_NF_FAULT_VOICE    2
+#define AGNN_NF_FAULT_ORDER    3
+#define AGNN_NF_FAULT_SCORES   4
+#define AGNN_NF_FAULT_WORDS    5
+typedef struct {
+  const int64_t* onset_div;      /* (device) [n_notes] */
+  const int64_t* duration_div;   /* (device) [n_notes] */
+  const int64_t* pitch;          /* (device) [n_notes] */
+  const int64_t* voice;          /* (device) [n_notes]; may be NULL for AGNN_NF_VOICE */
+  const int64_t* ts_beats;       /* (device) [n_notes] */
+  const int64_t* is_downbeat;    /* (device) [n_notes]; may be NULL for AGNN_NF_VOICE */
+  const float* onset_beat;       /* (device) [n_notes] */
+  const float* duration_beat;    /* (device) [n_notes] */
+  const uint8_t* is_note_onset;  /* (device) [n_notes] or NULL: all ones */
+  const int32_t* score_start;    /* (device) [n_scores + 1] */
+  int64_t n_notes;
+  int32_t n_scores;
+  int32_t feature_set;           /* AGNN_NF_VOICE | AGNN_NF_CADENCE */
+  float* x;                      /* (device) out fp32 [n_notes, 25 | 56], row stride ld_x */
+  int64_t ld_x;
+  int32_t* faults;               /* (device) int32[AGNN_NF_FAULT_WORDS] */
+} agnn_note_features_t;
+size_t agnn_note_features_workspace_bytes(int64_t n_notes, int32_t n_scores, int32_t feature_set);
+int agnn_note_features_f32(const agnn_note_features_t* f /* (host) */, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
