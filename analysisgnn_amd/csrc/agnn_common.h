@@ -100,17 +100,6 @@ __device__ __forceinline__ float wave_max_dpp(float v) {
   return fmaxf(fmaxf(lane_value(v, 0), lane_value(v, 16)), fmaxf(lane_value(v, 32), lane_value(v, 48)));
 }
 
-// Lane groups of the per-edge kernels (linkpred.hip, edgedec.hip): G = 4 .. 64 lanes of one wave own an edge or a row and cover its
-// H / 4 float4 columns; sums and flags cross the group by a butterfly, in a fixed order
-__device__ __forceinline__ float group_sum(float v, int G) {
-  for (int m = G >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-__device__ __forceinline__ int group_or(int v, int G) {
-  for (int m = G >> 1; m > 0; m >>= 1) v |= __shfl_xor(v, m);
-  return v;
-}
-
 // Philox-4x32-10 (Salmon et al. 2011): 4 x 32 random bits for counter (c0..c3), key (k0,k1).  The project's dropout masks:
 // counter = (element index lo, hi, call id, training step lo), key = (seed lo, seed hi ^ step hi).
 __device__ __forceinline__ uint4 philox(uint4 c, uint2 k) {
@@ -131,19 +120,12 @@ __device__ __forceinline__ uint4 stream_bits(uint64_t seed, uint64_t step, uint3
                 make_uint2(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32) ^ static_cast<uint32_t>(step >> 32)));
 }
 // Dropout at probability p drops a word below this threshold ...
-__device__ __forceinline__ uint32_t drop_threshold(float p) { return static_cast<uint32_t>(static_cast<double>(p) * 4294967296.0); }
+__host__ __device__ __forceinline__ uint32_t drop_threshold(float p) { return static_cast<uint32_t>(static_cast<double>(p) * 4294967296.0); }
 // ... and the factors of four words: 0 for a dropped element, `kept` (1 / (1 - p), or the caller's scale) otherwise
 __device__ __forceinline__ float4 keep_factors(uint4 r, uint32_t thr, float kept) {
   return make_float4(r.x >= thr ? kept : 0.f, r.y >= thr ? kept : 0.f, r.z >= thr ? kept : 0.f, r.w >= thr ? kept : 0.f);
 }
 #endif
-
-// log2 of the lanes per edge / row of those groups: the power of two in [4, 64] that covers H4 float4 columns (64 above 64 columns)
-inline int group_log2(int H4) {
-  int lg = 2;
-  while (lg < 6 && (1 << lg) < H4) ++lg;
-  return lg;
-}
 
 // wgrad.hip: fixed-order sum of S partial-result slabs (used by the weight-gradient kernels)
 int launch_slab_reduce(const float* slab, const float* slab_b, int S, int out_f, int in_f, int out_pad, int in_pad, float* dw,

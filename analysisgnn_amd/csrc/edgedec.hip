@@ -5,8 +5,9 @@
 // relation) and scatters the gradient with two index_add_ launches of float atomics.  `embed_r` is row-wise up to its dropout, so
 // here A_r = LN(ReLU(x W_r^T + b_r)) exists once per node (a column block of the stacked [B, R H] activation) and the dropout is
 // applied per (edge, end, column) in the pair kernel.  One call serves every relation of the step, as a table passed as kernel
-// argument; the conventions are those of linkpred.hip (groups of G = 4 .. 64 lanes covering H / 4 float4 columns, several
-// column passes above 64 columns; "alive" = both ends in [0, limit); no float atomics, fixed summation order).
+// argument; the conventions and their code are shared with linkpred.hip through peredge.h (groups of G = 4 .. 64 lanes covering
+// H / 4 float4 columns, several column passes above 64 columns; "alive" = both ends in [0, limit); the tile record and the
+// fixed-order final reduction; no float atomics).  Here: the keys draw, the masked product, pair_row and the cross entropy.
 //
 // Mask index.  The keep factors of edge e of relation r, end t (0 = source, 1 = destination), columns 4 q .. 4 q + 3 are the four
 // words of  stream_bits(seed, step, call_id, ((pos0_r + e) * 2 + t) * (H / 4) + q),  pos0_r = the global position of the
@@ -14,15 +15,14 @@
 // the two ends of an edge draw independent masks, as the reference's two Dropout calls do.  Backward regenerates them from the
 // (seed, step) pair the forward launch wrote to `rng_used`; nothing is stored.
 // agnn_edge_select_keys draws from the same stream at index pos0_r + e under a call id of its own.
-#include <algorithm>
 #include <cmath>
 
-#include "agnn_common.h"
+#include "peredge.h"
+
+using namespace agnn;
 
 namespace {
 
-constexpr int kTile = 64;       // edges per workgroup of the cross entropy (one lane of wave 0 each in the tile's reduction)
-constexpr int kPartWords = 6;   // loss sum (float bits) | alive, tp, fp, fn, tn
 constexpr int kBwdTile = 256;   // edges per workgroup of the cross entropy's backward
 constexpr int kMaxH = 512;
 
@@ -31,12 +31,9 @@ struct KeysDev {
   const int64_t* dst;
   int64_t* key;
   int64_t pos0;
-  int32_t E, limit, blk0, pad;
+  int32_t E, limit, first, pad;
 };
-struct KeysTable {
-  int32_t n_rel, pad;
-  KeysDev t[AGNN_MAX_SEG];
-};
+struct KeysTable : SegTable<KeysDev> {};
 
 struct PairFwdDev {
   const float* a;
@@ -47,33 +44,22 @@ struct PairFwdDev {
   int64_t ld_f;
   uint8_t* label;
   int64_t pos0;
-  int32_t E, limit, tile0, pad;
+  int32_t E, limit, first, pad;
 };
-struct PairFwdTable {
-  int32_t n_rel, pad;
-  PairFwdDev t[AGNN_MAX_SEG];
-};
+struct PairFwdTable : SegTable<PairFwdDev> {};
 
 struct PairBwdDev {
   const float* a;
   int64_t ld_a;
   const float* df;
   int64_t ld_df;
-  const int32_t* s_rowptr;
-  const int32_t* s_col;
-  const int32_t* s_perm;
-  const int32_t* d_rowptr;
-  const int32_t* d_col;
-  const int32_t* d_perm;
+  CsrDev s, d;                  // the edges by source and by destination
   float* da;
   int64_t ld_da;
   int64_t pos0;
-  int32_t n, E, limit, blk0;
+  int32_t n, E, limit, first;
 };
-struct PairBwdTable {
-  int32_t n_rel, pad;
-  PairBwdDev t[AGNN_MAX_SEG];
-};
+struct PairBwdTable : SegTable<PairBwdDev> {};
 
 struct CeFwdDev {
   const float* y;
@@ -83,22 +69,10 @@ struct CeFwdDev {
   const uint8_t* label;
   float* logit;
   float* dlogit;
-  int32_t E, limit, tile0, pad;
+  int32_t E, limit, first, pad;
 };
-struct CeFwdTable {
-  int32_t n_rel, pad;
-  CeFwdDev t[AGNN_MAX_SEG];
-};
-struct CeFinalDev {
-  float* loss;
-  float* inv_cnt;
-  int32_t* counts;
-  int32_t tile0, tiles;
-};
-struct CeFinalTable {
-  int32_t n_rel, pad;
-  CeFinalDev t[AGNN_MAX_SEG];
-};
+struct CeFwdTable : SegTable<CeFwdDev> {};
+struct CeFinalTable : SegTable<FinalDev> {};
 
 struct CeBwdDev {
   const float* y;
@@ -106,12 +80,9 @@ struct CeBwdDev {
   const float* dlogit;
   float* dy;
   int64_t ld_dy;
-  int32_t E, tile0;
+  int32_t E, first;
 };
-struct CeBwdTable {
-  int32_t n_rel, pad;
-  CeBwdDev t[AGNN_MAX_SEG];
-};
+struct CeBwdTable : SegTable<CeBwdDev> {};
 static_assert(sizeof(PairFwdTable) + 96 <= 4096 && sizeof(PairBwdTable) + 96 <= 4096 && sizeof(CeFwdTable) + 96 <= 4096 &&
               sizeof(CeBwdTable) + 96 <= 4096 && sizeof(KeysTable) + 96 <= 4096, "the tables travel as kernel arguments");
 
@@ -123,11 +94,11 @@ __device__ __forceinline__ float4 pair_mask(uint64_t seed, uint64_t step, uint32
 }
 
 __global__ __launch_bounds__(256) void k_edge_keys(KeysTable tab, const int64_t* __restrict__ rng, uint32_t call_id) {
-  int r = 0;
-  while (r + 1 < tab.n_rel && static_cast<int>(blockIdx.x) >= tab.t[r + 1].blk0) ++r;
+  int r;
+  find_segment(tab, r);
   const KeysDev& T = tab.t[r];
-  const int64_t e = static_cast<int64_t>(static_cast<int>(blockIdx.x) - T.blk0) * 256 + threadIdx.x;
-  if (e >= T.E) return;
+  const int64_t e = static_cast<int64_t>(static_cast<int>(blockIdx.x) - T.first) * 256 + threadIdx.x;
+  if (e >= T.E) return;                                    // one lane per edge and nothing after it: edge_ends' `in` has no use
   const int64_t s = T.src[e], d = T.dst[e];
   int64_t key = INT64_MAX;
   if (s >= 0 && d >= 0 && s < T.limit && d < T.limit) {
@@ -150,18 +121,17 @@ __global__ __launch_bounds__(256) void k_pair_fwd(PairFwdTable tab, int H4, int 
       rng_used[1] = static_cast<int64_t>(step);
     }
   }
-  int r = 0;
-  while (r + 1 < tab.n_rel && static_cast<int>(blockIdx.x) >= tab.t[r + 1].tile0) ++r;
+  int r;
+  find_segment(tab, r);
   const PairFwdDev& T = tab.t[r];
-  const int tile = static_cast<int>(blockIdx.x) - T.tile0;
-  const int G = 1 << lg, gpb = 256 >> lg;
-  const int grp = tid >> lg, lig = tid & (G - 1);
-  for (int le = grp; le < kTile; le += gpb) {             // the same trip count for every lane of the workgroup
+  const int tile = static_cast<int>(blockIdx.x) - T.first;
+  const Lanes L = lanes_of(lg);
+  const int G = L.G, lig = L.lig;
+  for (int le = L.grp; le < kTile; le += L.gpb) {         // the same trip count for every lane of the workgroup
     const int64_t e = static_cast<int64_t>(tile) * kTile + le;
-    const bool in = e < T.E;
-    int64_t s = 0, d = 0;
-    if (in) { s = T.src[e]; d = T.dst[e]; }
-    const bool alive = in && s >= 0 && d >= 0 && s < T.limit && d < T.limit;
+    const Ends x = edge_ends(T, e);
+    const int64_t s = x.s, d = x.d;
+    const bool in = x.in, alive = x.alive;
     int diff = 0;
     if (alive) {
       const float* as = T.a + s * T.ld_a;
@@ -189,9 +159,11 @@ __global__ __launch_bounds__(256) void k_pair_fwd(PairFwdTable tab, int H4, int 
 }
 
 // sum over row i of one CSR of df[perm] * m1 m2 * a[col], columns 4 c .. 4 c + 3, in list order
-__device__ __forceinline__ void pair_row(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int32_t* __restrict__ perm,
-                                         int i, const PairBwdDev& T, int H4, int c, uint32_t thr, float kept, uint64_t seed, uint64_t step,
-                                         uint32_t call_id, float4& acc) {
+__device__ __forceinline__ void pair_row(const CsrDev& csr, int i, const PairBwdDev& T, int H4, int c, uint32_t thr, float kept, uint64_t seed,
+                                         uint64_t step, uint32_t call_id, float4& acc) {
+  const int32_t* __restrict__ rowptr = csr.rowptr;
+  const int32_t* __restrict__ col = csr.col;
+  const int32_t* __restrict__ perm = csr.perm;
   const int r1 = rowptr[i + 1];
   for (int j = rowptr[i]; j < r1; ++j) {
     const int e = perm[j], o = col[j];
@@ -209,26 +181,24 @@ __device__ __forceinline__ void pair_row(const int32_t* __restrict__ rowptr, con
 
 __global__ __launch_bounds__(256) void k_pair_bwd(PairBwdTable tab, int H4, int lg, uint32_t thr, float kept, const int64_t* __restrict__ rng,
                                                   uint32_t call_id) {
-  const int tid = threadIdx.x;
-  int r = 0;
-  while (r + 1 < tab.n_rel && static_cast<int>(blockIdx.x) >= tab.t[r + 1].blk0) ++r;
+  int r;
+  find_segment(tab, r);
   const PairBwdDev& T = tab.t[r];
-  const int G = 1 << lg, gpb = 256 >> lg;
-  const int64_t row = static_cast<int64_t>(static_cast<int>(blockIdx.x) - T.blk0) * gpb + (tid >> lg);
+  const int64_t row = group_row(T, lg);
   if (row >= T.n) return;
   const int i = static_cast<int>(row);
-  const int lig = tid & (G - 1);
+  const Lanes L = lanes_of(lg);
   uint64_t seed = 0, step = 0;
   if (thr != 0u) {
     seed = static_cast<uint64_t>(rng[0]);
     step = static_cast<uint64_t>(rng[1]);
   }
   const bool live = T.E > 0 && i < T.limit;                // a row at or above the limit has no alive edge: zeros, no list is read
-  for (int c = lig; c < H4; c += G) {                      // H > 256: the row's lists are walked once per column pass
+  for (int c = L.lig; c < H4; c += L.G) {                  // H > 256: the row's lists are walked once per column pass
     float4 acc = agnn::f4_zero();
     if (live) {
-      pair_row(T.s_rowptr, T.s_col, T.s_perm, i, T, H4, c, thr, kept, seed, step, call_id, acc);
-      pair_row(T.d_rowptr, T.d_col, T.d_perm, i, T, H4, c, thr, kept, seed, step, call_id, acc);
+      pair_row(T.s, i, T, H4, c, thr, kept, seed, step, call_id, acc);
+      pair_row(T.d, i, T, H4, c, thr, kept, seed, step, call_id, acc);
     }
     *reinterpret_cast<float4*>(T.da + row * T.ld_da + 4 * c) = acc;
   }
@@ -240,19 +210,17 @@ __global__ __launch_bounds__(256) void k_ce_fwd(CeFwdTable tab, int H4, int lg, 
   __shared__ float x1_s[kTile];
   __shared__ int flag_s[kTile];
   const int tid = threadIdx.x;
-  int r = 0;
-  while (r + 1 < tab.n_rel && static_cast<int>(blockIdx.x) >= tab.t[r + 1].tile0) ++r;
+  int r;
+  find_segment(tab, r);
   const CeFwdDev& T = tab.t[r];
-  const int tile = static_cast<int>(blockIdx.x) - T.tile0;
-  const int G = 1 << lg, gpb = 256 >> lg;
-  const int grp = tid >> lg, lig = tid & (G - 1);
+  const int first = T.first, tile = static_cast<int>(blockIdx.x) - first;   // read once: the tile record takes it again
+  const Lanes L = lanes_of(lg);
+  const int G = L.G, lig = L.lig;
   const int H = 4 * H4;
-  for (int le = grp; le < kTile; le += gpb) {
+  for (int le = L.grp; le < kTile; le += L.gpb) {
     const int64_t e = static_cast<int64_t>(tile) * kTile + le;
-    const bool in = e < T.E;
-    int64_t s = 0, d = 0;
-    if (in) { s = T.src[e]; d = T.dst[e]; }
-    const bool alive = in && s >= 0 && d >= 0 && s < T.limit && d < T.limit;
+    const Ends x = edge_ends(T, e);
+    const bool in = x.in, alive = x.alive;
     float4 a0 = agnn::f4_zero(), a1 = agnn::f4_zero();
     if (alive) {
       const float* y = T.y + e * T.ld_y;
@@ -289,79 +257,37 @@ __global__ __launch_bounds__(256) void k_ce_fwd(CeFwdTable tab, int H4, int lg, 
       loss = -(q0 * l0 + q1 * l1);
       g0 = expf(l0) - q0;
       g1 = expf(l1) - q1;
-      const bool pos = z1 > z0;
-      code = 1 | ((pos && hit) ? 2 : 0) | ((pos && !hit) ? 4 : 0) | ((!pos && hit) ? 8 : 0) | ((!pos && !hit) ? 16 : 0);
+      code = confusion_code(z1 > z0, hit);
     }
     if (in) {
       const int64_t e = static_cast<int64_t>(tile) * kTile + tid;
       *reinterpret_cast<float2*>(T.logit + 2 * e) = make_float2(z0, z1);
       *reinterpret_cast<float2*>(T.dlogit + 2 * e) = make_float2(g0, g1);
     }
-    const float sum = agnn::wave_sum_dpp(loss);
-    uint32_t* p = part + (static_cast<int64_t>(T.tile0) + tile) * kPartWords;
-    const int c0 = __popcll(__ballot(code & 1)), c1 = __popcll(__ballot(code & 2)), c2 = __popcll(__ballot(code & 4));
-    const int c3 = __popcll(__ballot(code & 8)), c4 = __popcll(__ballot(code & 16));
-    if (tid == 0) {
-      p[0] = __float_as_uint(sum);
-      p[1] = c0; p[2] = c1; p[3] = c2; p[4] = c3; p[5] = c4;
-    }
+    tile_record(part, first, tile, loss, code);
   }
 }
 
-// one workgroup: relation after relation, the tiles' partial results in a fixed order (lane t takes tiles t, t + 256, ..., then
-// a tree in LDS), then the mean of the relations' losses in table order
+// one workgroup: relation after relation, then the mean of the relations' losses in table order
 __global__ __launch_bounds__(256) void k_ce_final(CeFinalTable tab, const uint32_t* __restrict__ part, float* __restrict__ total) {
-  __shared__ float f_s[256];
-  __shared__ int i_s[5][256];
   const int tid = threadIdx.x;
   float tot = 0.f;
-  for (int r = 0; r < tab.n_rel; ++r) {
-    const CeFinalDev& T = tab.t[r];
-    float acc = 0.f;
-    int c[5] = {0, 0, 0, 0, 0};
-    for (int t = tid; t < T.tiles; t += 256) {
-      const uint32_t* p = part + (static_cast<int64_t>(T.tile0) + t) * kPartWords;
-      acc += __uint_as_float(p[0]);
-#pragma unroll
-      for (int k = 0; k < 5; ++k) c[k] += static_cast<int>(p[1 + k]);
-    }
-    f_s[tid] = acc;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) i_s[k][tid] = c[k];
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if (tid < w) {
-        f_s[tid] += f_s[tid + w];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) i_s[k][tid] += i_s[k][tid + w];
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      const int alive = i_s[0][0];
-      const float inv = alive > 0 ? 1.f / static_cast<float>(alive) : 0.f;
-      const float l = f_s[0] * inv;
-      T.loss[0] = l;
-      T.inv_cnt[0] = inv;
-#pragma unroll
-      for (int k = 0; k < 5; ++k) T.counts[k] = i_s[k][0];
-      tot += l;
-    }
+  for (int r = 0; r < tab.n; ++r) {
+    segment_final(tab.t[r], part, &tot);
     __syncthreads();
   }
-  if (tid == 0) total[0] = tot / static_cast<float>(tab.n_rel);
+  if (tid == 0) total[0] = tot / static_cast<float>(tab.n);
 }
 
 // dy of a tile of kBwdTile edges; every group leaves its partial dw4 | db4 (2 H + 4 floats) in its own slot of the workspace
 __global__ __launch_bounds__(256) void k_ce_bwd(CeBwdTable tab, int H4, int lg, const float* __restrict__ w4, const float* __restrict__ scale,
                                                 float* __restrict__ slots) {
-  const int tid = threadIdx.x;
-  int r = 0;
-  while (r + 1 < tab.n_rel && static_cast<int>(blockIdx.x) >= tab.t[r + 1].tile0) ++r;
+  int r;
+  find_segment(tab, r);
   const CeBwdDev& T = tab.t[r];
-  const int tile = static_cast<int>(blockIdx.x) - T.tile0;
-  const int G = 1 << lg, gpb = 256 >> lg;
-  const int grp = tid >> lg, lig = tid & (G - 1);
+  const int tile = static_cast<int>(blockIdx.x) - T.first;
+  const Lanes L = lanes_of(lg);
+  const int G = L.G, gpb = L.gpb, grp = L.grp, lig = L.lig;
   const int H = 4 * H4;
   const float sc = scale[r];
   const int c0 = lig, c1 = lig + G;                        // H <= 512: at most two column passes of a 64-lane group
@@ -400,7 +326,7 @@ __global__ __launch_bounds__(256) void k_ce_bwd(CeBwdTable tab, int H4, int lg, 
       }
     }
   }
-  float* slot = slots + ((static_cast<int64_t>(T.tile0) + tile) * gpb + grp) * (2 * H + 4);
+  float* slot = slots + ((static_cast<int64_t>(T.first) + tile) * gpb + grp) * (2 * H + 4);
   if (has0) { *reinterpret_cast<float4*>(slot + 4 * c0) = pa0; *reinterpret_cast<float4*>(slot + H + 4 * c0) = pb0; }
   if (has1) { *reinterpret_cast<float4*>(slot + 4 * c1) = pa1; *reinterpret_cast<float4*>(slot + H + 4 * c1) = pb1; }
   if (lig == 0) *reinterpret_cast<float4*>(slot + 2 * H) = make_float4(sb0, sb1, 0.f, 0.f);
@@ -444,71 +370,37 @@ __global__ __launch_bounds__(256) void k_ce_bwd_reduce(const float* __restrict__
   }
 }
 
-// agnn::drop_threshold on the host; 0 stands for "no dropout" in the kernels, so a p > 0 below 2^-32 still draws
-inline uint32_t threshold_for(float p) {
-  return p > 0.f ? std::max<uint32_t>(static_cast<uint32_t>(static_cast<double>(p) * 4294967296.0), 1u) : 0u;
-}
+const char* const kNoun = "relation";
 
-int check_h(const char* who, int32_t H) {
-  if (H < 4 || H > kMaxH || H % 4 != 0) return agnn::fail(AGNN_EINVAL, "%s: H=%d must be a multiple of 4 in [4, %d]", who, H, kMaxH);
-  return AGNN_OK;
-}
+// what every entry point checks of a relation's sizes
+int check_rel(const char* who, int i, int64_t E, int64_t n, int64_t limit) { return check_sizes(who, kNoun, i, E, n, limit, kBwdTile); }
 
-int check_n_rel(const char* who, int32_t n_rel) {
-  if (n_rel < 0 || n_rel > AGNN_MAX_SEG) return agnn::fail(AGNN_EINVAL, "%s: n_rel=%d must be in [0, %d]", who, n_rel, AGNN_MAX_SEG);
-  return AGNN_OK;
-}
-
-// a [rows, H] float matrix a kernel reads or writes with float4
-int check_rows(const char* who, int i, const char* name, const void* p, int64_t ld, int32_t H) {
-  using namespace agnn;
-  if (!p) return fail(AGNN_EINVAL, "%s: relation %d: %s is null", who, i, name);
-  if (ld < H) return fail(AGNN_EINVAL, "%s: relation %d: ld_%s=%lld < H=%d", who, i, name, (long long)ld, H);
-  if (ld % 4 != 0) return fail(AGNN_EALIGN, "%s: relation %d: ld_%s=%lld is not a multiple of 4", who, i, name, (long long)ld);
-  if (!aligned16(p)) return fail(AGNN_EALIGN, "%s: relation %d: %s is not 16-byte aligned", who, i, name);
-  return AGNN_OK;
-}
-
-int check_sizes(const char* who, int i, int64_t E, int64_t n, int64_t limit) {
-  using namespace agnn;
-  if (E < 0 || E > INT32_MAX - kBwdTile) return fail(AGNN_EINVAL, "%s: relation %d: E=%lld must be in [0, 2^31 - 256)", who, i, (long long)E);
-  if (n < 0 || n > INT32_MAX) return fail(AGNN_EINVAL, "%s: relation %d: n=%lld must be in [0, 2^31)", who, i, (long long)n);
-  if (limit < 0 || limit > n) return fail(AGNN_EINVAL, "%s: relation %d: limit=%lld must be in [0, n=%lld]", who, i, (long long)limit, (long long)n);
-  return AGNN_OK;
-}
-
-int64_t ce_tiles(int32_t n_rel, const agnn_edge_ce_t* rels) {
+template <typename Rel>
+int64_t tiles_of_all(int32_t n_rel, const Rel* rels, int tile) {
   int64_t tiles = 0;
-  for (int i = 0; i < n_rel; ++i) tiles += rels[i].E > 0 ? (rels[i].E + kTile - 1) / kTile : 0;
+  for (int i = 0; i < n_rel; ++i) tiles += tiles_of(rels[i].E, tile);
   return tiles;
-}
-
-int64_t ce_bwd_slots(int32_t n_rel, const agnn_edge_ce_bwd_t* rels, int32_t H) {
-  int64_t tiles = 0;
-  for (int i = 0; i < n_rel; ++i) tiles += rels[i].E > 0 ? (rels[i].E + kBwdTile - 1) / kBwdTile : 0;
-  return tiles * (256 >> agnn::group_log2(H / 4));
 }
 
 }  // namespace
 
 extern "C" int agnn_edge_select_keys(int32_t n_rel, const agnn_edge_keys_t* rels, const int64_t* rng_state, uint32_t call_id,
                                      agnn_stream_t stream_) {
-  using namespace agnn;
   const char* who = "edge_select_keys";
-  if (int rc = check_n_rel(who, n_rel)) return rc;
+  if (int rc = check_segments(who, "n_rel", n_rel)) return rc;
   if (n_rel == 0) return AGNN_OK;
   if (!rels) return fail(AGNN_EINVAL, "%s: rels is null", who);
   KeysTable tab;
-  tab.n_rel = n_rel;
+  tab.n = n_rel;
   tab.pad = 0;
   int64_t blocks = 0;
   for (int i = 0; i < n_rel; ++i) {
     const agnn_edge_keys_t& t = rels[i];
-    if (int rc = check_sizes(who, i, t.E, INT32_MAX, t.limit)) return rc;
+    if (int rc = check_rel(who, i, t.E, INT32_MAX, t.limit)) return rc;
     if (t.pos0 < 0) return fail(AGNN_EINVAL, "%s: relation %d: pos0=%lld is negative", who, i, (long long)t.pos0);
     if (t.E > 0 && (!t.src || !t.dst || !t.key)) return fail(AGNN_EINVAL, "%s: relation %d: src / dst / key is null", who, i);
     const int64_t nb = (t.E + 255) / 256;
-    if (blocks + nb > INT32_MAX) return fail(AGNN_EINVAL, "%s: more than 2^31 - 1 workgroups", who);
+    if (int rc = check_grid(who, "workgroups", blocks + nb)) return rc;
     tab.t[i] = KeysDev{t.src, t.dst, t.key, t.pos0, static_cast<int32_t>(t.E), static_cast<int32_t>(t.limit), static_cast<int32_t>(blocks), 0};
     blocks += nb;
   }
@@ -521,42 +413,41 @@ extern "C" int agnn_edge_select_keys(int32_t n_rel, const agnn_edge_keys_t* rels
 extern "C" int agnn_edge_pair_fwd_f32(int32_t n_rel, const agnn_edge_pair_t* rels, int32_t H, const int64_t* labels, int32_t K,
                                       int64_t ld_labels, float p, const int64_t* rng_state, uint32_t call_id, int64_t* rng_used,
                                       agnn_stream_t stream_) {
-  using namespace agnn;
   const char* who = "edge_pair_fwd";
-  if (int rc = check_h(who, H)) return rc;
-  if (int rc = check_n_rel(who, n_rel)) return rc;
+  if (int rc = check_h(who, H, kMaxH)) return rc;
+  if (int rc = check_segments(who, "n_rel", n_rel)) return rc;
   if (!(p >= 0.f && p < 1.f)) return fail(AGNN_EINVAL, "%s: p=%g must be in [0, 1)", who, static_cast<double>(p));
   if (K < 0) return fail(AGNN_EINVAL, "%s: K=%d is negative", who, K);
   if (n_rel == 0) return AGNN_OK;
   if (!rels) return fail(AGNN_EINVAL, "%s: rels is null", who);
   if (!labels) K = 0;
   PairFwdTable tab;
-  tab.n_rel = n_rel;
+  tab.n = n_rel;
   tab.pad = 0;
   int64_t tiles = 0;
   for (int i = 0; i < n_rel; ++i) {
     const agnn_edge_pair_t& t = rels[i];
-    if (int rc = check_sizes(who, i, t.E, t.n, t.limit)) return rc;
+    if (int rc = check_rel(who, i, t.E, t.n, t.limit)) return rc;
     if (t.pos0 < 0) return fail(AGNN_EINVAL, "%s: relation %d: pos0=%lld is negative", who, i, (long long)t.pos0);
     const int64_t nt = (t.E + kTile - 1) / kTile;
     if (t.E > 0) {
       if (!t.src || !t.dst) return fail(AGNN_EINVAL, "%s: relation %d: src / dst is null", who, i);
       if (!t.label) return fail(AGNN_EINVAL, "%s: relation %d: label is null", who, i);
-      if (int rc = check_rows(who, i, "f", t.f, t.ld_f, H)) return rc;
+      if (int rc = check_rows(who, kNoun, i, "f", t.f, t.ld_f, H)) return rc;
       if (t.limit > 0) {
-        if (int rc = check_rows(who, i, "a", t.a, t.ld_a, H)) return rc;
+        if (int rc = check_rows(who, kNoun, i, "a", t.a, t.ld_a, H)) return rc;
         if (K > 0 && ld_labels < t.limit)
           return fail(AGNN_EINVAL, "%s: relation %d: ld_labels=%lld < limit=%lld", who, i, (long long)ld_labels, (long long)t.limit);
       }
     }
-    if (tiles + nt > INT32_MAX) return fail(AGNN_EINVAL, "%s: more than 2^31 - 1 tiles of edges", who);
+    if (int rc = check_grid(who, "tiles of edges", tiles + nt)) return rc;
     tab.t[i] = PairFwdDev{t.a, t.ld_a, t.src, t.dst, t.f, t.ld_f, t.label, t.pos0, static_cast<int32_t>(t.E), static_cast<int32_t>(t.limit),
                           static_cast<int32_t>(tiles), 0};
     tiles += nt;
   }
   if (tiles == 0) return AGNN_OK;
   if (p > 0.f && !rng_state) return fail(AGNN_EINVAL, "%s: rng_state is null with p=%g", who, static_cast<double>(p));
-  const uint32_t thr = threshold_for(p);
+  const uint32_t thr = threshold_or_none(p);
   hipLaunchKernelGGL(k_pair_fwd, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, static_cast<hipStream_t>(stream_), tab, H / 4,
                      agnn::group_log2(H / 4), labels, K, ld_labels, thr, 1.f / (1.f - p), rng_state, call_id, rng_used);
   return check_launch(who);
@@ -564,41 +455,40 @@ extern "C" int agnn_edge_pair_fwd_f32(int32_t n_rel, const agnn_edge_pair_t* rel
 
 extern "C" int agnn_edge_pair_bwd_f32(int32_t n_rel, const agnn_edge_pair_bwd_t* rels, int32_t H, float p, const int64_t* rng_state,
                                       uint32_t call_id, agnn_stream_t stream_) {
-  using namespace agnn;
   const char* who = "edge_pair_bwd";
-  if (int rc = check_h(who, H)) return rc;
-  if (int rc = check_n_rel(who, n_rel)) return rc;
+  if (int rc = check_h(who, H, kMaxH)) return rc;
+  if (int rc = check_segments(who, "n_rel", n_rel)) return rc;
   if (!(p >= 0.f && p < 1.f)) return fail(AGNN_EINVAL, "%s: p=%g must be in [0, 1)", who, static_cast<double>(p));
   if (n_rel == 0) return AGNN_OK;
   if (!rels) return fail(AGNN_EINVAL, "%s: rels is null", who);
   PairBwdTable tab;
-  tab.n_rel = n_rel;
+  tab.n = n_rel;
   tab.pad = 0;
   const int lg = agnn::group_log2(H / 4), gpb = 256 >> lg;
   int64_t blocks = 0;
   for (int i = 0; i < n_rel; ++i) {
     const agnn_edge_pair_bwd_t& t = rels[i];
-    if (int rc = check_sizes(who, i, t.E, t.n, t.limit)) return rc;
+    if (int rc = check_rel(who, i, t.E, t.n, t.limit)) return rc;
     if (t.pos0 < 0) return fail(AGNN_EINVAL, "%s: relation %d: pos0=%lld is negative", who, i, (long long)t.pos0);
     const int64_t nb = (t.n + gpb - 1) / gpb;
     if (t.n > 0) {
-      if (int rc = check_rows(who, i, "da", t.da, t.ld_da, H)) return rc;
+      if (int rc = check_rows(who, kNoun, i, "da", t.da, t.ld_da, H)) return rc;
       if (t.E > 0 && t.limit > 0) {
         if (!t.s_rowptr || !t.d_rowptr) return fail(AGNN_EINVAL, "%s: relation %d: s_rowptr / d_rowptr is null", who, i);
         if (!t.s_col || !t.s_perm || !t.d_col || !t.d_perm) return fail(AGNN_EINVAL, "%s: relation %d: a col / perm array is null", who, i);
-        if (int rc = check_rows(who, i, "a", t.a, t.ld_a, H)) return rc;
-        if (int rc = check_rows(who, i, "df", t.df, t.ld_df, H)) return rc;
+        if (int rc = check_rows(who, kNoun, i, "a", t.a, t.ld_a, H)) return rc;
+        if (int rc = check_rows(who, kNoun, i, "df", t.df, t.ld_df, H)) return rc;
       }
     }
-    if (blocks + nb > INT32_MAX) return fail(AGNN_EINVAL, "%s: more than 2^31 - 1 workgroups", who);
-    tab.t[i] = PairBwdDev{t.a, t.ld_a, t.df, t.ld_df, t.s_rowptr, t.s_col, t.s_perm, t.d_rowptr, t.d_col, t.d_perm, t.da, t.ld_da, t.pos0,
+    if (int rc = check_grid(who, "workgroups", blocks + nb)) return rc;
+    tab.t[i] = PairBwdDev{t.a, t.ld_a, t.df, t.ld_df, {t.s_rowptr, t.s_col, t.s_perm}, {t.d_rowptr, t.d_col, t.d_perm}, t.da, t.ld_da, t.pos0,
                           static_cast<int32_t>(t.n), static_cast<int32_t>(t.limit > 0 ? t.E : 0), static_cast<int32_t>(t.limit),
                           static_cast<int32_t>(blocks)};
     blocks += nb;
   }
   if (blocks == 0) return AGNN_OK;
   if (p > 0.f && !rng_state) return fail(AGNN_EINVAL, "%s: rng_state is null with p=%g", who, static_cast<double>(p));
-  const uint32_t thr = threshold_for(p);
+  const uint32_t thr = threshold_or_none(p);
   hipLaunchKernelGGL(k_pair_bwd, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream_), tab, H / 4, lg, thr,
                      1.f / (1.f - p), rng_state, call_id);
   return check_launch(who);
@@ -606,27 +496,26 @@ extern "C" int agnn_edge_pair_bwd_f32(int32_t n_rel, const agnn_edge_pair_bwd_t*
 
 extern "C" size_t agnn_edge_ce_workspace_bytes(int32_t n_rel, const agnn_edge_ce_t* rels) {
   if (n_rel <= 0 || n_rel > AGNN_MAX_SEG || !rels) return 0;
-  return static_cast<size_t>(ce_tiles(n_rel, rels)) * kPartWords * sizeof(uint32_t);
+  return static_cast<size_t>(tiles_of_all(n_rel, rels, kTile)) * kPartWords * sizeof(uint32_t);
 }
 
 extern "C" int agnn_edge_ce_fwd_f32(int32_t n_rel, const agnn_edge_ce_t* rels, int32_t H, const float* w4, const float* b4, float smoothing,
                                     float* total, void* workspace, size_t workspace_bytes, agnn_stream_t stream_) {
-  using namespace agnn;
   const char* who = "edge_ce_fwd";
-  if (int rc = check_h(who, H)) return rc;
-  if (int rc = check_n_rel(who, n_rel)) return rc;
+  if (int rc = check_h(who, H, kMaxH)) return rc;
+  if (int rc = check_segments(who, "n_rel", n_rel)) return rc;
   if (!(smoothing >= 0.f && smoothing <= 1.f)) return fail(AGNN_EINVAL, "%s: smoothing=%g must be in [0, 1]", who, static_cast<double>(smoothing));
   if (n_rel == 0) return AGNN_OK;
   if (!rels) return fail(AGNN_EINVAL, "%s: rels is null", who);
   if (!total) return fail(AGNN_EINVAL, "%s: total is null", who);
   CeFwdTable tab;
   CeFinalTable fin;
-  tab.n_rel = fin.n_rel = n_rel;
+  tab.n = fin.n = n_rel;
   tab.pad = fin.pad = 0;
   int64_t tiles = 0;
   for (int i = 0; i < n_rel; ++i) {
     const agnn_edge_ce_t& t = rels[i];
-    if (int rc = check_sizes(who, i, t.E, INT32_MAX, t.limit)) return rc;
+    if (int rc = check_rel(who, i, t.E, INT32_MAX, t.limit)) return rc;
     if (!t.loss || !t.inv_cnt || !t.counts) return fail(AGNN_EINVAL, "%s: relation %d: loss / inv_cnt / counts is null", who, i);
     const int64_t nt = (t.E + kTile - 1) / kTile;
     if (t.E > 0) {
@@ -636,22 +525,20 @@ extern "C" int agnn_edge_ce_fwd_f32(int32_t n_rel, const agnn_edge_ce_t* rels, i
         return fail(AGNN_EALIGN, "%s: relation %d: logit / dlogit is not 8-byte aligned", who, i);
       if (t.limit > 0) {
         if (!t.label) return fail(AGNN_EINVAL, "%s: relation %d: label is null", who, i);
-        if (int rc = check_rows(who, i, "y", t.y, t.ld_y, H)) return rc;
+        if (int rc = check_rows(who, kNoun, i, "y", t.y, t.ld_y, H)) return rc;
       }
     }
-    if (tiles + nt > INT32_MAX) return fail(AGNN_EINVAL, "%s: more than 2^31 - 1 tiles of edges", who);
+    if (int rc = check_grid(who, "tiles of edges", tiles + nt)) return rc;
     tab.t[i] = CeFwdDev{t.y, t.ld_y, t.src, t.dst, t.label, t.logit, t.dlogit, static_cast<int32_t>(t.E), static_cast<int32_t>(t.limit),
                         static_cast<int32_t>(tiles), 0};
-    fin.t[i] = CeFinalDev{t.loss, t.inv_cnt, t.counts, static_cast<int32_t>(tiles), static_cast<int32_t>(nt)};
+    fin.t[i] = FinalDev{t.loss, t.inv_cnt, t.counts, static_cast<int32_t>(tiles), static_cast<int32_t>(nt)};
     tiles += nt;
   }
   const size_t need = static_cast<size_t>(tiles) * kPartWords * sizeof(uint32_t);
   if (tiles > 0) {
     if (!w4 || !b4) return fail(AGNN_EINVAL, "%s: w4 / b4 is null", who);
     if (!aligned16(w4)) return fail(AGNN_EALIGN, "%s: w4 is not 16-byte aligned", who);
-    if (!workspace) return fail(AGNN_EINVAL, "%s: workspace is null", who);
-    if (workspace_bytes < need) return fail(AGNN_ENOMEM, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
-    if ((reinterpret_cast<uintptr_t>(workspace) & 3u) != 0) return fail(AGNN_EALIGN, "%s: workspace is not 4-byte aligned", who);
+    if (int rc = check_workspace(who, workspace, workspace_bytes, need, 4)) return rc;
   }
   hipStream_t s = static_cast<hipStream_t>(stream_);
   uint32_t* part = static_cast<uint32_t*>(workspace);
@@ -665,35 +552,34 @@ extern "C" int agnn_edge_ce_fwd_f32(int32_t n_rel, const agnn_edge_ce_t* rels, i
 
 extern "C" size_t agnn_edge_ce_bwd_workspace_bytes(int32_t n_rel, const agnn_edge_ce_bwd_t* rels, int32_t H) {
   if (n_rel <= 0 || n_rel > AGNN_MAX_SEG || !rels || H < 4 || H > kMaxH || H % 4 != 0) return 0;
-  return static_cast<size_t>(ce_bwd_slots(n_rel, rels, H)) * (2 * H + 4) * sizeof(float);
+  return static_cast<size_t>(tiles_of_all(n_rel, rels, kBwdTile) * (256 >> group_log2(H / 4))) * (2 * H + 4) * sizeof(float);
 }
 
 extern "C" int agnn_edge_ce_bwd_f32(int32_t n_rel, const agnn_edge_ce_bwd_t* rels, int32_t H, const float* w4, const float* scale,
                                     float* dw4, float* db4, void* workspace, size_t workspace_bytes, agnn_stream_t stream_) {
-  using namespace agnn;
   const char* who = "edge_ce_bwd";
-  if (int rc = check_h(who, H)) return rc;
-  if (int rc = check_n_rel(who, n_rel)) return rc;
+  if (int rc = check_h(who, H, kMaxH)) return rc;
+  if (int rc = check_segments(who, "n_rel", n_rel)) return rc;
   if (n_rel == 0) return AGNN_OK;
   if (!rels) return fail(AGNN_EINVAL, "%s: rels is null", who);
   if (!dw4 || !db4) return fail(AGNN_EINVAL, "%s: dw4 / db4 is null", who);
   if (!aligned16(dw4)) return fail(AGNN_EALIGN, "%s: dw4 is not 16-byte aligned", who);
   CeBwdTable tab;
-  tab.n_rel = n_rel;
+  tab.n = n_rel;
   tab.pad = 0;
   const int lg = agnn::group_log2(H / 4), gpb = 256 >> lg;
   int64_t tiles = 0;
   for (int i = 0; i < n_rel; ++i) {
     const agnn_edge_ce_bwd_t& t = rels[i];
-    if (int rc = check_sizes(who, i, t.E, INT32_MAX, 0)) return rc;
+    if (int rc = check_rel(who, i, t.E, INT32_MAX, 0)) return rc;
     const int64_t nt = (t.E + kBwdTile - 1) / kBwdTile;
     if (t.E > 0) {
       if (!t.dlogit) return fail(AGNN_EINVAL, "%s: relation %d: dlogit is null", who, i);
       if (reinterpret_cast<uintptr_t>(t.dlogit) & 7u) return fail(AGNN_EALIGN, "%s: relation %d: dlogit is not 8-byte aligned", who, i);
-      if (int rc = check_rows(who, i, "y", t.y, t.ld_y, H)) return rc;
-      if (int rc = check_rows(who, i, "dy", t.dy, t.ld_dy, H)) return rc;
+      if (int rc = check_rows(who, kNoun, i, "y", t.y, t.ld_y, H)) return rc;
+      if (int rc = check_rows(who, kNoun, i, "dy", t.dy, t.ld_dy, H)) return rc;
     }
-    if ((tiles + nt) * gpb > INT32_MAX) return fail(AGNN_EINVAL, "%s: more than 2^31 - 1 partial slots", who);
+    if (int rc = check_grid(who, "partial slots", (tiles + nt) * gpb)) return rc;
     tab.t[i] = CeBwdDev{t.y, t.ld_y, t.dlogit, t.dy, t.ld_dy, static_cast<int32_t>(t.E), static_cast<int32_t>(tiles)};
     tiles += nt;
   }
@@ -702,9 +588,7 @@ extern "C" int agnn_edge_ce_bwd_f32(int32_t n_rel, const agnn_edge_ce_bwd_t* rel
   if (tiles > 0) {
     if (!w4 || !scale) return fail(AGNN_EINVAL, "%s: w4 / scale is null", who);
     if (!aligned16(w4)) return fail(AGNN_EALIGN, "%s: w4 is not 16-byte aligned", who);
-    if (!workspace) return fail(AGNN_EINVAL, "%s: workspace is null", who);
-    if (workspace_bytes < need) return fail(AGNN_ENOMEM, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
-    if (!aligned16(workspace)) return fail(AGNN_EALIGN, "%s: workspace is not 16-byte aligned", who);
+    if (int rc = check_workspace(who, workspace, workspace_bytes, need, 16)) return rc;
   }
   hipStream_t s = static_cast<hipStream_t>(stream_);
   float* slots = static_cast<float*>(workspace);

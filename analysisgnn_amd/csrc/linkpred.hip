@@ -16,14 +16,16 @@
 // agnn_link_bce_bwd_f32: dz[i] = scale (sum_{e: s_e = i} g_e z[d_e] + sum_{e: d_e = i} g_e z[s_e]) as a gather-reduce over the
 //   candidate list's two CSRs, one row of dz per group, the coefficient fetched through `perm`: every row is written exactly
 //   once (no zero fill, no atomics); a self loop appears in both CSRs and so contributes 2 g_e z[i].
+// The table, the lane groups, the ends of an edge, the tile record, the final reduction and the argument checks are peredge.h,
+// shared with edgedec.hip; here are the dot product, the membership scan, the BCE and link_row's walk.
 #include <cmath>
 
-#include "agnn_common.h"
+#include "peredge.h"
+
+using namespace agnn;
 
 namespace {
 
-constexpr int kTile = 64;       // candidates per workgroup (one lane of wave 0 each in the tile's reduction)
-constexpr int kPartWords = 6;   // loss sum (float bits) | alive, tp, fp, fn, tn
 constexpr int kU = 4;           // list entries a group of the backward keeps in flight
 
 struct LinkFwdDev {
@@ -36,62 +38,42 @@ struct LinkFwdDev {
   float* logit;
   uint8_t* label;
   float* g;
-  int32_t E, limit, tile0, pad;
+  int32_t E, limit, first, pad;
 };
-struct LinkFwdTable {
-  int32_t n_tasks, pad;
-  LinkFwdDev t[AGNN_MAX_SEG];
-};
-
-struct LinkFinalDev {
-  float* loss;
-  float* inv_cnt;
-  int32_t* counts;
-  int32_t tile0, tiles;
-};
-struct LinkFinalTable {
-  LinkFinalDev t[AGNN_MAX_SEG];
+struct LinkFwdTable : SegTable<LinkFwdDev> {};
+struct LinkFinalTable {         // one workgroup per task: no lookup, no count
+  FinalDev t[AGNN_MAX_SEG];
 };
 
 struct LinkBwdDev {
   const float* z;
   int64_t ld_z;
   const float* g;
-  const int32_t* s_rowptr;
-  const int32_t* s_col;
-  const int32_t* s_perm;
-  const int32_t* d_rowptr;
-  const int32_t* d_col;
-  const int32_t* d_perm;
+  CsrDev s, d;                  // the candidates by source and by destination
   float* dz;
   int64_t ld_dz;
-  int32_t n, E, blk0, pad;
+  int32_t n, E, first, pad;
 };
-struct LinkBwdTable {
-  int32_t n_tasks, pad;
-  LinkBwdDev t[AGNN_MAX_SEG];
-};
+struct LinkBwdTable : SegTable<LinkBwdDev> {};
 static_assert(sizeof(LinkFwdTable) + 64 <= 4096 && sizeof(LinkBwdTable) + 64 <= 4096, "the tables travel as kernel arguments");
 
 __global__ __launch_bounds__(256) void k_link_fwd(LinkFwdTable tab, int H4, int lg, uint32_t* __restrict__ part) {
   __shared__ float x_s[kTile];
   __shared__ int flag_s[kTile];
   const int tid = threadIdx.x;
-  int task = 0;
-  while (task + 1 < tab.n_tasks && static_cast<int>(blockIdx.x) >= tab.t[task + 1].tile0) ++task;
+  int task;
+  find_segment(tab, task);
   const LinkFwdDev& T = tab.t[task];
-  const int tile = static_cast<int>(blockIdx.x) - T.tile0;
-  const int G = 1 << lg, gpb = 256 >> lg;
-  const int grp = tid >> lg, lig = tid & (G - 1);
+  const int first = T.first, tile = static_cast<int>(blockIdx.x) - first;   // read once: the tile record takes it again
+  const Lanes L = lanes_of(lg);
+  const int G = L.G, lig = L.lig;
   const float* __restrict__ z = T.z;
   // Instruction issue bounds this launch, not memory latency (four candidates in flight per group made it slower): a group only
   // gathers and reduces; what one lane per candidate can do — the BCE, the stores — waits for wave 0, one lane per candidate.
-  for (int le = grp; le < kTile; le += gpb) {             // the same trip count for every lane of the workgroup
-    const int64_t e = static_cast<int64_t>(tile) * kTile + le;
-    const bool in = e < T.E;
-    int64_t s = 0, d = 0;
-    if (in) { s = T.src[e]; d = T.dst[e]; }
-    const bool alive = in && s >= 0 && d >= 0 && s < T.limit && d < T.limit;
+  for (int le = L.grp; le < kTile; le += L.gpb) {         // the same trip count for every lane of the workgroup
+    const Ends x = edge_ends(T, static_cast<int64_t>(tile) * kTile + le);
+    const int64_t s = x.s, d = x.d;
+    const bool in = x.in, alive = x.alive;
     float4 a = agnn::f4_zero();
     int hit = 0;
     if (alive) {
@@ -106,10 +88,10 @@ __global__ __launch_bounds__(256) void k_link_fwd(LinkFwdTable tab, int H4, int 
       const int32_t d32 = static_cast<int32_t>(d);
       for (int j = T.t_rowptr[s] + lig; j < r1; j += G) hit |= (T.t_col[j] == d32) ? 1 : 0;
     }
-    const float x = agnn::group_sum((a.x + a.y) + (a.z + a.w), G);
+    const float dot = agnn::group_sum((a.x + a.y) + (a.z + a.w), G);
     hit = agnn::group_or(hit, G);
     if (lig == 0) {
-      x_s[le] = x;
+      x_s[le] = dot;
       flag_s[le] = (in ? 1 : 0) | (alive ? 2 : 0) | (hit ? 4 : 0);
     }
   }
@@ -126,8 +108,7 @@ __global__ __launch_bounds__(256) void k_link_fwd(LinkFwdTable tab, int H4, int 
       loss = fmaxf(x, 0.f) - x * y + log1pf(t);
       const float sg = x >= 0.f ? 1.f / (1.f + t) : t / (1.f + t);
       gg = sg - y;
-      const bool pos = x > 0.f;
-      code = 1 | ((pos && hit) ? 2 : 0) | ((pos && !hit) ? 4 : 0) | ((!pos && hit) ? 8 : 0) | ((!pos && !hit) ? 16 : 0);
+      code = confusion_code(x > 0.f, hit);
     }
     if (in) {
       const int64_t e = static_cast<int64_t>(tile) * kTile + tid;
@@ -135,57 +116,22 @@ __global__ __launch_bounds__(256) void k_link_fwd(LinkFwdTable tab, int H4, int 
       T.label[e] = static_cast<uint8_t>((alive && hit) ? 1 : 0);
       T.g[e] = gg;
     }
-    const float sum = agnn::wave_sum_dpp(loss);
-    uint32_t* p = part + (static_cast<int64_t>(T.tile0) + tile) * kPartWords;
-    const int c0 = __popcll(__ballot(code & 1)), c1 = __popcll(__ballot(code & 2)), c2 = __popcll(__ballot(code & 4));
-    const int c3 = __popcll(__ballot(code & 8)), c4 = __popcll(__ballot(code & 16));
-    if (tid == 0) {
-      p[0] = __float_as_uint(sum);
-      p[1] = c0; p[2] = c1; p[3] = c2; p[4] = c3; p[5] = c4;
-    }
+    tile_record(part, first, tile, loss, code);
   }
 }
 
-// one workgroup per task: the tiles' partial results in a fixed order (lane t takes tiles t, t + 256, ..., then a tree in LDS)
+// one workgroup per task
 __global__ __launch_bounds__(256) void k_link_final(LinkFinalTable tab, const uint32_t* __restrict__ part) {
-  __shared__ float f_s[256];
-  __shared__ int i_s[5][256];
-  const int tid = threadIdx.x;
-  const LinkFinalDev& T = tab.t[blockIdx.x];
-  float acc = 0.f;
-  int c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;
-  for (int t = tid; t < T.tiles; t += 256) {
-    const uint32_t* p = part + (static_cast<int64_t>(T.tile0) + t) * kPartWords;
-    acc += __uint_as_float(p[0]);
-    c0 += static_cast<int>(p[1]); c1 += static_cast<int>(p[2]); c2 += static_cast<int>(p[3]);
-    c3 += static_cast<int>(p[4]); c4 += static_cast<int>(p[5]);
-  }
-  f_s[tid] = acc;
-  i_s[0][tid] = c0; i_s[1][tid] = c1; i_s[2][tid] = c2; i_s[3][tid] = c3; i_s[4][tid] = c4;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) {
-      f_s[tid] += f_s[tid + w];
-#pragma unroll
-      for (int k = 0; k < 5; ++k) i_s[k][tid] += i_s[k][tid + w];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const int alive = i_s[0][0];
-    const float inv = alive > 0 ? 1.f / static_cast<float>(alive) : 0.f;
-    T.loss[0] = f_s[0] * inv;
-    T.inv_cnt[0] = inv;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) T.counts[k] = i_s[k][0];
-  }
+  segment_final(tab.t[blockIdx.x], part);
 }
 
 // sum over row i of one CSR of g[perm] z[col], columns 4 c .. 4 c + 3
-__device__ __forceinline__ void link_row(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int32_t* __restrict__ perm,
-                                         int i, const float* __restrict__ g, const float* __restrict__ z, int64_t ld_z, int n, int E, int c,
-                                         float4& acc) {
+__device__ __forceinline__ void link_row(const CsrDev csr, int i, const float* __restrict__ g, const float* __restrict__ z, int64_t ld_z, int n,
+                                         int E, int c, float4& acc) {
   if (E <= 0) return;                                      // no candidate: g and z may be absent
+  const int32_t* __restrict__ rowptr = csr.rowptr;
+  const int32_t* __restrict__ col = csr.col;
+  const int32_t* __restrict__ perm = csr.perm;
   const int r1 = rowptr[i + 1];
   // kU entries in flight, added in list order as one at a time would be.  The loads are unconditional (an idle slot reads the
   // row's last entry, a skipped one g[0] / row 0, and drops it): a load under a condition becomes a branch with its own wait.
@@ -221,35 +167,25 @@ __device__ __forceinline__ void link_row(const int32_t* __restrict__ rowptr, con
 }
 
 __global__ __launch_bounds__(256) void k_link_bwd(LinkBwdTable tab, int H4, int lg, const float* __restrict__ scale) {
-  const int tid = threadIdx.x;
-  int task = 0;
-  while (task + 1 < tab.n_tasks && static_cast<int>(blockIdx.x) >= tab.t[task + 1].blk0) ++task;
+  int task;
+  find_segment(tab, task);
   const LinkBwdDev& T = tab.t[task];
-  const int G = 1 << lg, gpb = 256 >> lg;
-  const int64_t row = static_cast<int64_t>(static_cast<int>(blockIdx.x) - T.blk0) * gpb + (tid >> lg);
+  const int64_t row = group_row(T, lg);
   if (row >= T.n) return;
   const int i = static_cast<int>(row);
-  const int lig = tid & (G - 1);
+  const Lanes L = lanes_of(lg);
   const float sc = scale[task];
-  for (int c = lig; c < H4; c += G) {                      // H > 256: the row's lists are walked once per column pass
+  for (int c = L.lig; c < H4; c += L.G) {                      // H > 256: the row's lists are walked once per column pass
     float4 acc = agnn::f4_zero();
-    link_row(T.s_rowptr, T.s_col, T.s_perm, i, T.g, T.z, T.ld_z, T.n, T.E, c, acc);
-    link_row(T.d_rowptr, T.d_col, T.d_perm, i, T.g, T.z, T.ld_z, T.n, T.E, c, acc);
+    link_row(T.s, i, T.g, T.z, T.ld_z, T.n, T.E, c, acc);
+    link_row(T.d, i, T.g, T.z, T.ld_z, T.n, T.E, c, acc);
     *reinterpret_cast<float4*>(T.dz + row * T.ld_dz + 4 * c) = make_float4(sc * acc.x, sc * acc.y, sc * acc.z, sc * acc.w);
   }
 }
 
-int check_h(const char* who, int32_t H) {
-  if (H < 4 || H % 4 != 0) return agnn::fail(AGNN_EINVAL, "%s: H=%d must be a positive multiple of 4", who, H);
-  return AGNN_OK;
-}
-
 int check_fwd_task(const agnn_link_task_t& t, int i, int32_t H) {
-  using namespace agnn;
   const char* who = "link_bce_fwd";
-  if (t.E < 0 || t.E > INT32_MAX - kTile) return fail(AGNN_EINVAL, "%s: task %d: E=%lld must be in [0, 2^31 - 64)", who, i, (long long)t.E);
-  if (t.n < 0 || t.n > INT32_MAX) return fail(AGNN_EINVAL, "%s: task %d: n=%lld must be in [0, 2^31)", who, i, (long long)t.n);
-  if (t.limit < 0 || t.limit > t.n) return fail(AGNN_EINVAL, "%s: task %d: limit=%lld must be in [0, n=%lld]", who, i, (long long)t.limit, (long long)t.n);
+  if (int rc = check_sizes(who, "task", i, t.E, t.n, t.limit, kTile)) return rc;
   if (!t.loss || !t.inv_cnt || !t.counts) return fail(AGNN_EINVAL, "%s: task %d: loss / inv_cnt / counts is null", who, i);
   if (t.E == 0) return AGNN_OK;
   if (!t.src || !t.dst) return fail(AGNN_EINVAL, "%s: task %d: src / dst is null", who, i);
@@ -257,72 +193,62 @@ int check_fwd_task(const agnn_link_task_t& t, int i, int32_t H) {
   if (t.limit == 0) return AGNN_OK;                        // no candidate is alive: no row is read
   if (!t.z) return fail(AGNN_EINVAL, "%s: task %d: z is null", who, i);
   if (!t.t_rowptr || !t.t_col) return fail(AGNN_EINVAL, "%s: task %d: t_rowptr / t_col is null", who, i);
-  if (t.ld_z < H) return fail(AGNN_EINVAL, "%s: task %d: ld_z=%lld < H=%d", who, i, (long long)t.ld_z, H);
-  if (t.ld_z % 4 != 0) return fail(AGNN_EALIGN, "%s: task %d: ld_z=%lld is not a multiple of 4", who, i, (long long)t.ld_z);
-  if (!aligned16(t.z)) return fail(AGNN_EALIGN, "%s: task %d: z is not 16-byte aligned", who, i);
-  return AGNN_OK;
-}
-
-int64_t fwd_tiles(int32_t n_tasks, const agnn_link_task_t* tasks) {
-  int64_t tiles = 0;
-  for (int i = 0; i < n_tasks; ++i) tiles += tasks[i].E > 0 ? (tasks[i].E + kTile - 1) / kTile : 0;
-  return tiles;
+  return check_rows(who, "task", i, "z", t.z, t.ld_z, H);
 }
 
 }  // namespace
 
 extern "C" size_t agnn_link_bce_workspace_bytes(int32_t n_tasks, const agnn_link_task_t* tasks) {
   if (n_tasks <= 0 || n_tasks > AGNN_MAX_SEG || !tasks) return 0;
-  return static_cast<size_t>(fwd_tiles(n_tasks, tasks)) * kPartWords * sizeof(uint32_t);
+  int64_t tiles = 0;
+  for (int i = 0; i < n_tasks; ++i) tiles += tiles_of(tasks[i].E, kTile);
+  return static_cast<size_t>(tiles) * kPartWords * sizeof(uint32_t);
 }
 
 extern "C" int agnn_link_bce_fwd_f32(int32_t n_tasks, const agnn_link_task_t* tasks, int32_t H, void* workspace, size_t workspace_bytes,
                                      agnn_stream_t stream_) {
-  using namespace agnn;
-  if (int rc = check_h("link_bce_fwd", H)) return rc;
-  if (n_tasks < 0 || n_tasks > AGNN_MAX_SEG) return fail(AGNN_EINVAL, "link_bce_fwd: n_tasks=%d must be in [0, %d]", n_tasks, AGNN_MAX_SEG);
+  const char* who = "link_bce_fwd";
+  if (int rc = check_h(who, H)) return rc;
+  if (int rc = check_segments(who, "n_tasks", n_tasks)) return rc;
   if (n_tasks == 0) return AGNN_OK;
-  if (!tasks) return fail(AGNN_EINVAL, "link_bce_fwd: tasks is null");
+  if (!tasks) return fail(AGNN_EINVAL, "%s: tasks is null", who);
   LinkFwdTable tab;
   LinkFinalTable fin;
-  tab.n_tasks = n_tasks;
+  tab.n = n_tasks;
   tab.pad = 0;
   int64_t tiles = 0;
   for (int i = 0; i < n_tasks; ++i) {
     const agnn_link_task_t& t = tasks[i];
     if (int rc = check_fwd_task(t, i, H)) return rc;
-    const int64_t nt = t.E > 0 ? (t.E + kTile - 1) / kTile : 0;
-    if (tiles + nt > INT32_MAX) return fail(AGNN_EINVAL, "link_bce_fwd: more than 2^31 - 1 tiles of candidates");
+    const int64_t nt = tiles_of(t.E, kTile);
+    if (int rc = check_grid(who, "tiles of candidates", tiles + nt)) return rc;
     tab.t[i] = LinkFwdDev{t.z, t.ld_z, t.src, t.dst, t.t_rowptr, t.t_col, t.logit, t.label, t.g, static_cast<int32_t>(t.E),
                           static_cast<int32_t>(t.limit), static_cast<int32_t>(tiles), 0};
-    fin.t[i] = LinkFinalDev{t.loss, t.inv_cnt, t.counts, static_cast<int32_t>(tiles), static_cast<int32_t>(nt)};
+    fin.t[i] = FinalDev{t.loss, t.inv_cnt, t.counts, static_cast<int32_t>(tiles), static_cast<int32_t>(nt)};
     tiles += nt;
   }
   const size_t need = static_cast<size_t>(tiles) * kPartWords * sizeof(uint32_t);
   if (tiles > 0) {
-    if (!workspace) return fail(AGNN_EINVAL, "link_bce_fwd: workspace is null");
-    if (workspace_bytes < need) return fail(AGNN_ENOMEM, "link_bce_fwd: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    if ((reinterpret_cast<uintptr_t>(workspace) & 3u) != 0) return fail(AGNN_EALIGN, "link_bce_fwd: workspace is not 4-byte aligned");
+    if (int rc = check_workspace(who, workspace, workspace_bytes, need, 4)) return rc;
   }
   hipStream_t s = static_cast<hipStream_t>(stream_);
   uint32_t* part = static_cast<uint32_t*>(workspace);
   if (tiles > 0) {
     hipLaunchKernelGGL(k_link_fwd, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, s, tab, H / 4, agnn::group_log2(H / 4), part);
-    if (int rc = check_launch("link_bce_fwd")) return rc;
+    if (int rc = check_launch(who)) return rc;
   }
   hipLaunchKernelGGL(k_link_final, dim3(static_cast<unsigned>(n_tasks)), dim3(256), 0, s, fin, part);
   return check_launch("link_bce_fwd (final pass)");
 }
 
 extern "C" int agnn_link_bce_bwd_f32(int32_t n_tasks, const agnn_link_bwd_t* tasks, int32_t H, const float* scale, agnn_stream_t stream_) {
-  using namespace agnn;
   const char* who = "link_bce_bwd";
   if (int rc = check_h(who, H)) return rc;
-  if (n_tasks < 0 || n_tasks > AGNN_MAX_SEG) return fail(AGNN_EINVAL, "%s: n_tasks=%d must be in [0, %d]", who, n_tasks, AGNN_MAX_SEG);
+  if (int rc = check_segments(who, "n_tasks", n_tasks)) return rc;
   if (n_tasks == 0) return AGNN_OK;
   if (!tasks) return fail(AGNN_EINVAL, "%s: tasks is null", who);
   LinkBwdTable tab;
-  tab.n_tasks = n_tasks;
+  tab.n = n_tasks;
   tab.pad = 0;
   const int lg = agnn::group_log2(H / 4), gpb = 256 >> lg;
   int64_t blocks = 0;
@@ -334,19 +260,15 @@ extern "C" int agnn_link_bce_bwd_f32(int32_t n_tasks, const agnn_link_bwd_t* tas
     if (t.n > 0) {
       if (!t.dz) return fail(AGNN_EINVAL, "%s: task %d: dz is null", who, i);
       if (!t.s_rowptr || !t.d_rowptr) return fail(AGNN_EINVAL, "%s: task %d: s_rowptr / d_rowptr is null", who, i);
-      if (t.ld_dz < H) return fail(AGNN_EINVAL, "%s: task %d: ld_dz=%lld < H=%d", who, i, (long long)t.ld_dz, H);
-      if (t.ld_dz % 4 != 0) return fail(AGNN_EALIGN, "%s: task %d: ld_dz=%lld is not a multiple of 4", who, i, (long long)t.ld_dz);
-      if (!aligned16(t.dz)) return fail(AGNN_EALIGN, "%s: task %d: dz is not 16-byte aligned", who, i);
+      if (int rc = check_rows(who, "task", i, "dz", t.dz, t.ld_dz, H)) return rc;
       if (t.E > 0) {
         if (!t.z || !t.g) return fail(AGNN_EINVAL, "%s: task %d: z / g is null", who, i);
         if (!t.s_col || !t.s_perm || !t.d_col || !t.d_perm) return fail(AGNN_EINVAL, "%s: task %d: a col / perm array is null", who, i);
-        if (t.ld_z < H) return fail(AGNN_EINVAL, "%s: task %d: ld_z=%lld < H=%d", who, i, (long long)t.ld_z, H);
-        if (t.ld_z % 4 != 0) return fail(AGNN_EALIGN, "%s: task %d: ld_z=%lld is not a multiple of 4", who, i, (long long)t.ld_z);
-        if (!aligned16(t.z)) return fail(AGNN_EALIGN, "%s: task %d: z is not 16-byte aligned", who, i);
+        if (int rc = check_rows(who, "task", i, "z", t.z, t.ld_z, H)) return rc;
       }
     }
-    if (blocks + nb > INT32_MAX) return fail(AGNN_EINVAL, "%s: more than 2^31 - 1 workgroups", who);
-    tab.t[i] = LinkBwdDev{t.z, t.ld_z, t.g, t.s_rowptr, t.s_col, t.s_perm, t.d_rowptr, t.d_col, t.d_perm, t.dz, t.ld_dz,
+    if (int rc = check_grid(who, "workgroups", blocks + nb)) return rc;
+    tab.t[i] = LinkBwdDev{t.z, t.ld_z, t.g, {t.s_rowptr, t.s_col, t.s_perm}, {t.d_rowptr, t.d_col, t.d_perm}, t.dz, t.ld_dz,
                           static_cast<int32_t>(t.n), static_cast<int32_t>(t.E), static_cast<int32_t>(blocks), 0};
     blocks += nb;
   }

@@ -19,20 +19,21 @@ boolean-mask compactions and a CPU `randperm` that read a size back per relation
 
 Departure from the reference, deliberate (the same as `pretrain.link_bce`): a relation WITHOUT an alive edge has loss 0 and zero
 gradient — torch's cross entropy over nothing is NaN, which would poison the flat gradient buffer.  It still counts in the
-division by the number of relations, and its alive count of 0 is returned (`parts["alive"]`)."""
+division by the number of relations, and its alive count of 0 is returned (`parts["alive"]`).  What this objective shares with
+`pretrain.link_bce` is `analysisgnn_amd/peredge.py` on the host (edge-list check, alive mask, CSRs by either end, loss outputs,
+a gradient through the logits) and csrc/peredge.h on the device."""
 from __future__ import annotations
 
-import copy
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn as nn
 
-from . import _lib, fused
+from . import _lib, fused, peredge
 from .fused import grouped_norm_act, norm_act
-from .graph import Csr, EdgeType, SegSpec, build_csr
-from .heads import _cat_params
+from .graph import Csr, EdgeType, build_csr
+from .heads import _cat_params, deepcopy_without_last
 from .linear import linear
 
 __all__ = ["EdgeDecoder", "EdgePlan", "edge_plan", "edge_consistency_loss", "RNA_KEYS", "SELECT_CALL_ID"]
@@ -64,18 +65,6 @@ class EdgePlan:
         return self.src[self.e_off[r]:self.e_off[r + 1]], self.dst[self.e_off[r]:self.e_off[r + 1]]
 
 
-def _pair(e, what: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    if isinstance(e, torch.Tensor):
-        if e.dim() != 2 or e.shape[0] != 2:
-            raise _lib.AgnnError(f"{what}: int64 [2, E] expected (a PyG edge_index), got {tuple(e.shape)}")
-        s, d = e[0], e[1]
-    else:
-        s, d = e
-    if s.dtype != torch.int64 or d.dtype != torch.int64 or s.dim() != 1 or s.shape != d.shape:
-        raise _lib.AgnnError(f"{what}: two int64 [E] index vectors expected")
-    return s, d
-
-
 def edge_plan(edge_index_dict: Dict[EdgeType, Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]], batch_size: int,
               n_rows: Optional[int] = None, select: bool = True, rng: Optional[torch.Tensor] = None, call_id: Optional[int] = None,
               relations: Optional[Sequence[str]] = None) -> EdgePlan:
@@ -98,53 +87,46 @@ def edge_plan(edge_index_dict: Dict[EdgeType, Union[torch.Tensor, Tuple[torch.Te
         raise _lib.AgnnError("edge_plan: no note-note relation to plan")
     if len(names) > _lib.MAX_SEG:
         raise _lib.AgnnError(f"edge_plan: {len(names)} relations, at most {_lib.MAX_SEG} per call")
-    lists = [_pair(edge_index_dict[found[r]], f"edge_plan: {r}") for r in names]
+    lists = [peredge.edge_index(edge_index_dict[found[r]], f"edge_plan: {r}") for r in names]
     dev = _lib.require_gpu(*[t for p in lists for t in p])
-    lists = [(s.contiguous(), d.contiguous()) for s, d in lists]
     drawn = [i for i, (s, _) in enumerate(lists) if select and s.numel() > bs]
     picks = {}
     if drawn:
         rng = fused.rng_state(dev) if rng is None else rng
         if rng.dtype != torch.int64 or rng.numel() != 2 or rng.device != dev:
             raise _lib.AgnnError("edge_plan: rng is a device int64[2] = (seed, step)")
-        pos0, off = [], 0
-        for s, _ in lists:
-            pos0.append(off)
-            off += int(s.numel())
-        keys = torch.empty((sum(int(lists[i][0].numel()) for i in drawn),), dtype=torch.int64, device=dev)
+        pos0 = peredge.offsets(s.numel() for s, _ in lists)
+        k_off = peredge.offsets(lists[i][0].numel() for i in drawn)
+        keys = torch.empty((k_off[-1],), dtype=torch.int64, device=dev)
         tab = (_lib.EdgeKeys * len(drawn))()
-        k_off = [0]
         for j, i in enumerate(drawn):
             s, d = lists[i]
             t = tab[j]
-            t.src, t.dst, t.E, t.limit, t.pos0, t.key = s.data_ptr(), d.data_ptr(), int(s.numel()), limit, pos0[i], keys[k_off[-1]:].data_ptr()
-            k_off.append(k_off[-1] + int(s.numel()))
+            t.src, t.dst, t.E, t.limit, t.pos0, t.key = s.data_ptr(), d.data_ptr(), int(s.numel()), limit, pos0[i], keys[k_off[j]:].data_ptr()
         _lib.check(_lib.load().agnn_edge_select_keys(len(drawn), tab, rng.data_ptr(), (SELECT_CALL_ID if call_id is None else int(call_id)) & 0xFFFFFFFF,
                                                      _lib.stream_ptr(dev)), "agnn_edge_select_keys")
         for j, i in enumerate(drawn):
             val, idx = torch.topk(keys[k_off[j]:k_off[j + 1]], bs, largest=False, sorted=True)
             picks[i] = (val, idx)
-    srcs, dsts, oks, e_off = [], [], [], [0]
+    srcs, dsts, oks = [], [], []
     for i, (s, d) in enumerate(lists):
         if i in picks:
             val, idx = picks[i]
             s, d = s[idx], d[idx]
             ok = val != INT64_MAX          # fewer than batch_size alive edges: the tail of the cut is not alive
         else:
-            ok = (s >= 0) & (d >= 0) & (s < limit) & (d < limit)
+            ok = peredge.alive_mask(s, d, limit)
         srcs.append(s)
         dsts.append(d)
         oks.append(ok)
-        e_off.append(e_off[-1] + int(s.numel()))
-    ok = torch.cat(oks)
+    ok, e_off = torch.cat(oks), peredge.offsets(s.numel() for s in srcs)
     out = torch.full((1,), n_rows, dtype=torch.int64, device=dev)
     # "dropped" folded into the ids the CSR build sees (as postprocess does with row = n): out of range, so left out of every row
     src = torch.where(ok, torch.cat(srcs), out).contiguous()
     dst = torch.where(ok, torch.cat(dsts), out).contiguous()
     specs = []
     for r in range(len(names)):
-        s, d = src[e_off[r]:e_off[r + 1]], dst[e_off[r]:e_off[r + 1]]
-        specs += [SegSpec(row=s, col=d, n_rows=n_rows), SegSpec(row=d, col=s, n_rows=n_rows)]
+        specs += peredge.end_specs(src[e_off[r]:e_off[r + 1]], dst[e_off[r]:e_off[r + 1]], n_rows)
     csrs = build_csr(specs)
     return EdgePlan(relations=names, edge_types=[found[r] for r in names], src=src, dst=dst, e_off=e_off, n_rows=n_rows, limit=limit,
                     by_src=csrs[0::2], by_dst=csrs[1::2])
@@ -196,9 +178,7 @@ class _EdgePair(torch.autograd.Function):
             t.a, t.ld_a, t.n = (a.data_ptr() + 4 * r * H if a.numel() else None), max(a.stride(0), R * H), plan.n_rows
             t.df, t.ld_df = (df[lo:].data_ptr() if n else None), max(df.stride(0), H)
             t.E, t.limit, t.pos0 = n, plan.limit, lo
-            s, d = plan.by_src[r], plan.by_dst[r]
-            t.s_rowptr, t.s_col, t.s_perm = s.rowptr.data_ptr(), s.col.data_ptr(), s.perm.data_ptr()
-            t.d_rowptr, t.d_col, t.d_perm = d.rowptr.data_ptr(), d.col.data_ptr(), d.perm.data_ptr()
+            peredge.fill_csr(t, plan.by_src[r], plan.by_dst[r])
             t.da, t.ld_da = (da.data_ptr() + 4 * r * H if da.numel() else None), R * H
         _lib.check(_lib.load().agnn_edge_pair_bwd_f32(R, tab, H, p, _lib.ptr(used[0]) if used else None, call_id, _lib.stream_ptr(dev)),
                    "agnn_edge_pair_bwd_f32")
@@ -218,17 +198,15 @@ class _EdgeCE(torch.autograd.Function):
         label = info["edge_labels"]
         logit = torch.empty((E, 2), dtype=torch.float32, device=dev)
         dlogit = torch.empty((E, 2), dtype=torch.float32, device=dev)
-        stats = torch.empty((2, R), dtype=torch.float32, device=dev)            # mean loss | 1 / alive count
-        counts = torch.empty((R, 5), dtype=torch.int32, device=dev)             # alive, tp, fp, fn, tn
         total = torch.empty((), dtype=torch.float32, device=dev)
         tab = (_lib.EdgeCe * R)()
+        stats, counts = peredge.loss_outputs(tab, dev)
         for r in range(R):
             t, lo, n = tab[r], plan.e_off[r], plan.e_off[r + 1] - plan.e_off[r]
             t.y, t.ld_y = (y[lo:].data_ptr() if n else None), max(y.stride(0), H)
             t.src, t.dst, t.label = (plan.src[lo:].data_ptr(), plan.dst[lo:].data_ptr(), label[lo:].data_ptr()) if n else (None, None, None)
             t.E, t.limit = n, plan.limit
             t.logit, t.dlogit = (logit[lo:].data_ptr(), dlogit[lo:].data_ptr()) if n else (None, None)
-            t.loss, t.inv_cnt, t.counts = stats[0, r:].data_ptr(), stats[1, r:].data_ptr(), counts[r].data_ptr()
         nws = int(lib.agnn_edge_ce_workspace_bytes(R, tab))
         ws = torch.empty((max(nws, 4),), dtype=torch.uint8, device=dev)
         _lib.check(lib.agnn_edge_ce_fwd_f32(R, tab, H, w4.data_ptr(), b4.data_ptr(), float(smoothing), total.data_ptr(), ws.data_ptr(), nws,
@@ -250,13 +228,8 @@ class _EdgeCE(torch.autograd.Function):
         R, E = len(plan.relations), plan.n_edges
         scale = (g_total.to(torch.float32) * stats[1] / R).contiguous() if g_total is not None else torch.zeros(R, dtype=torch.float32, device=dev)
         if g_logit is not None:
-            # a gradient arriving through the logits themselves: folded into the per-edge coefficient (edges that are not alive
-            # have the constant logits 0), and the kernel's scale becomes one
-            sizes = [plan.e_off[r + 1] - plan.e_off[r] for r in range(R)]
-            per_edge = torch.cat([scale[r:r + 1].expand(n) for r, n in enumerate(sizes)]) if E else scale[:0]
-            alive = ((plan.src < plan.limit) & (plan.dst < plan.limit) & (plan.src >= 0) & (plan.dst >= 0)).unsqueeze(1)
-            dlogit = (dlogit * per_edge.unsqueeze(1) + g_logit.to(torch.float32) * alive).contiguous()
-            scale = torch.ones(R, dtype=torch.float32, device=dev)
+            ends = [plan.edges(r) + (plan.limit,) for r in range(R)]
+            dlogit, scale = peredge.fold_logit_grad(dlogit, scale, plan.e_off, g_logit.split([s.numel() for s, _, _ in ends]), ends)
         dy = torch.empty((E, H), dtype=torch.float32, device=dev)
         dw4 = torch.empty((2, H), dtype=torch.float32, device=dev)
         db4 = torch.empty((2,), dtype=torch.float32, device=dev)
@@ -288,13 +261,7 @@ class EdgeDecoder(nn.Module):
         self.fc = nn.Sequential(nn.Linear(channels, channels), nn.ReLU(), nn.LayerNorm(channels), nn.Dropout(dropout), nn.Linear(channels, 2))
         self.last: dict = {}
 
-    def __deepcopy__(self, memo):
-        cls = self.__class__
-        new = cls.__new__(cls)
-        memo[id(self)] = new
-        for k, v in self.__dict__.items():
-            new.__dict__[k] = {} if k == "last" else copy.deepcopy(v, memo)     # `last` holds a call's graph, not state
-        return new
+    __deepcopy__ = deepcopy_without_last
 
     @property
     def relations(self) -> List[str]:

@@ -13,6 +13,7 @@ weight-gradient GEMMs are 64 x 128 outputs with K = N (4 workgroups on a 256-CU 
 """
 from __future__ import annotations
 
+import copy
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -68,6 +69,15 @@ def _cat_params(ps, stack: bool = False) -> torch.Tensor:
     ps = list(ps)
     t = stack_rows(ps) if stack else cat_rows(ps)
     return mark_wgrad_async(t, deferrable=True, leaves=ps) if all(p.is_leaf for p in ps) else t
+
+
+def deepcopy_without_last(self, memo):
+    """`__deepcopy__` of a module whose `last` holds a call's graph, not state (PreEncoder, EdgeDecoder): the copy's is empty."""
+    new = self.__class__.__new__(self.__class__)
+    memo[id(self)] = new
+    for k, v in self.__dict__.items():
+        new.__dict__[k] = {} if k == "last" else copy.deepcopy(v, memo)
+    return new
 
 
 HEADS_FUSED = False      # one launch for the whole head block (csrc/heads.hip).  Correct, but 148 us against 141 us for the three launches

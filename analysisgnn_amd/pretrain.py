@@ -24,8 +24,8 @@ Departures from the reference, both deliberate:
   not depend on their order.  Logits and labels come back in the order of `cat(onset, consecutive)`.
 
 Out of scope: `FAMO` (the reference's own call `FAMO(n_tasks=4, ...)` does not match its constructor, SURVEY A.7: the effective
-objective is the plain sum built here), the Lightning optimizer plumbing.  (`EdgeDecoder`, which reuses the per-edge machinery
-here, is `analysisgnn_amd/edge_loss.py`.)"""
+objective is the plain sum built here), the Lightning optimizer plumbing.  (`EdgeDecoder` is `analysisgnn_amd/edge_loss.py`; what
+the two per-edge objectives share lives in `analysisgnn_amd/peredge.py` on the host and csrc/peredge.h on the device.)"""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -34,10 +34,10 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib, heads
+from . import _lib, heads, peredge
 from .fused import grouped_norm_act
 from .graph import Csr, EdgeType, SegSpec, build_csr
-from .heads import _cat_params, grouped_projection, multitask_cross_entropy
+from .heads import _cat_params, deepcopy_without_last, grouped_projection, multitask_cross_entropy
 from .hgt import HybridHGT
 from .linear import linear
 from .metrics import MultiTaskMetrics
@@ -69,14 +69,6 @@ class LinkPlan:
         return int(self.cand.shape[1])
 
 
-def _edges_arg(e: Optional[torch.Tensor], dev, what: str) -> torch.Tensor:
-    if e is None:
-        return torch.zeros((2, 0), dtype=torch.int64, device=dev)
-    if e.dim() != 2 or e.shape[0] != 2 or e.dtype != torch.int64:
-        raise _lib.AgnnError(f"{what}: int64 [2, E] expected (a PyG edge_index), got {e.dtype} {tuple(e.shape)}")
-    return e.contiguous()
-
-
 def link_plans(tasks: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], n_rows: int, limit: Optional[int] = None) -> List[LinkPlan]:
     """Plans of several link tasks over feature matrices of `n_rows` rows, their 3 CSRs each in ONE `agnn_csr_build` call.
     `tasks`: (candidates int64 [2, E], true edges int64 [2, E_true] or None) per task.  Candidate ends outside [0, n_rows) never
@@ -90,12 +82,11 @@ def link_plans(tasks: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], n_r
     dev = _lib.require_gpu(*[t[0] for t in tasks])
     specs, cands = [], []
     for cand, true in tasks:
-        cand = _edges_arg(cand, dev, "link_plan: candidates")
-        true = _edges_arg(true, dev, "link_plan: true edges")
+        cand = peredge.edge_index(cand, "link_plan: candidates", dev)
+        true = peredge.edge_index(true, "link_plan: true edges", dev)
         _lib.require_gpu(cand, true)
         cands.append((cand, true))
-        specs += [SegSpec(row=cand[0], col=cand[1], n_rows=n_rows), SegSpec(row=cand[1], col=cand[0], n_rows=n_rows),
-                  SegSpec(row=true[0], col=true[1], n_rows=n_rows)]
+        specs += peredge.end_specs(cand[0], cand[1], n_rows) + [SegSpec(row=true[0], col=true[1], n_rows=n_rows)]
     csrs = build_csr(specs)
     return [LinkPlan(cand=c, n_rows=n_rows, limit=limit, by_src=csrs[3 * i], by_dst=csrs[3 * i + 1], true=csrs[3 * i + 2], keep=[t])
             for i, (c, t) in enumerate(cands)]
@@ -104,11 +95,6 @@ def link_plans(tasks: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], n_r
 def link_plan(candidates: torch.Tensor, true_edges: Optional[torch.Tensor], n_rows: int, limit: Optional[int] = None) -> LinkPlan:
     """`link_plans` for one task."""
     return link_plans([(candidates, true_edges)], n_rows, limit)[0]
-
-
-def _alive_mask(p: LinkPlan) -> torch.Tensor:
-    c = p.cand
-    return (c[0] >= 0) & (c[1] >= 0) & (c[0] < p.limit) & (c[1] < p.limit)
 
 
 class _LinkBCE(torch.autograd.Function):
@@ -125,15 +111,12 @@ class _LinkBCE(torch.autograd.Function):
         for p, z in zip(plans, feats):
             if z.shape[1] != H or z.shape[0] != p.n_rows:
                 raise _lib.AgnnError(f"link_bce: features {tuple(z.shape)} for a plan over {p.n_rows} rows (one width H={H} per call)")
-        e_off = [0]
-        for p in plans:
-            e_off.append(e_off[-1] + p.n_edges)
+        e_off = peredge.offsets(p.n_edges for p in plans)
         logit = torch.empty((e_off[-1],), dtype=torch.float32, device=dev)
         label = torch.empty((e_off[-1],), dtype=torch.uint8, device=dev)
         g = torch.empty((e_off[-1],), dtype=torch.float32, device=dev)
-        stats = torch.empty((2, K), dtype=torch.float32, device=dev)          # mean loss | 1 / alive count
-        counts = torch.empty((K, 5), dtype=torch.int32, device=dev)           # alive, tp, fp, fn, tn
         tab = (_lib.LinkTask * K)()
+        stats, counts = peredge.loss_outputs(tab, dev)
         for i, (p, z) in enumerate(zip(plans, feats)):
             t, E, lo = tab[i], p.n_edges, e_off[i]
             t.z, t.ld_z, t.n = (z.data_ptr() if z.numel() else None), z.stride(0) if z.shape[0] > 1 else max(z.stride(0), H), p.n_rows
@@ -141,7 +124,6 @@ class _LinkBCE(torch.autograd.Function):
             t.E, t.limit = E, p.limit
             t.t_rowptr, t.t_col = p.true.rowptr.data_ptr(), p.true.col.data_ptr()
             t.logit, t.label, t.g = (logit[lo:].data_ptr(), label[lo:].data_ptr(), g[lo:].data_ptr()) if E else (None, None, None)
-            t.loss, t.inv_cnt, t.counts = stats[0, i:].data_ptr(), stats[1, i:].data_ptr(), counts[i].data_ptr()
         nws = int(lib.agnn_link_bce_workspace_bytes(K, tab))
         ws = torch.empty((max(nws, 4),), dtype=torch.uint8, device=dev)
         _lib.check(lib.agnn_link_bce_fwd_f32(K, tab, H, ws.data_ptr(), nws, _lib.stream_ptr(dev)), "agnn_link_bce_fwd_f32")
@@ -164,24 +146,14 @@ class _LinkBCE(torch.autograd.Function):
             return (None, None) + (None,) * K
         scale = (g_loss.to(torch.float32) * stats[1]).contiguous() if g_loss is not None else torch.zeros(K, dtype=torch.float32, device=dev)
         if any(t is not None for t in g_logits):
-            # a gradient arriving through the logits themselves: folded into the per-candidate coefficient (candidates that are
-            # not alive have the constant logit 0), and the kernel's scale becomes one
-            parts = []
-            for i, p in enumerate(plans):
-                c = g[e_off[i]:e_off[i + 1]] * scale[i]
-                if g_logits[i] is not None:
-                    c = c + g_logits[i].to(torch.float32) * _alive_mask(p)
-                parts.append(c)
-            g = torch.cat(parts) if parts else g
-            scale = torch.ones(K, dtype=torch.float32, device=dev)
+            g, scale = peredge.fold_logit_grad(g, scale, e_off, g_logits, [(p.cand[0], p.cand[1], p.limit) for p in plans])
         dzs = [torch.empty((p.n_rows, H), dtype=torch.float32, device=dev) for p in plans]
         tab = (_lib.LinkBwd * K)()
         for i, (p, z, dz) in enumerate(zip(plans, feats, dzs)):
             t, E = tab[i], p.n_edges
             t.z, t.ld_z, t.n = (z.data_ptr() if z.numel() else None), z.stride(0) if z.shape[0] > 1 else max(z.stride(0), H), p.n_rows
             t.g, t.E = (g[e_off[i]:].data_ptr() if E else None), E
-            t.s_rowptr, t.s_col, t.s_perm = p.by_src.rowptr.data_ptr(), p.by_src.col.data_ptr(), p.by_src.perm.data_ptr()
-            t.d_rowptr, t.d_col, t.d_perm = p.by_dst.rowptr.data_ptr(), p.by_dst.col.data_ptr(), p.by_dst.perm.data_ptr()
+            peredge.fill_csr(t, p.by_src, p.by_dst)
             t.dz, t.ld_dz = (dz.data_ptr() if dz.numel() else None), H
         _lib.check(_lib.load().agnn_link_bce_bwd_f32(K, tab, H, scale.data_ptr(), _lib.stream_ptr(dev)), "agnn_link_bce_bwd_f32")
         return (None, None) + tuple(dzs)
@@ -240,14 +212,7 @@ class PreEncoder(nn.Module):
         self.spelling_clf = _head(out_channels, self.pitch_spelling_classes)
         self.last: dict = {}
 
-    def __deepcopy__(self, memo):
-        cls = self.__class__
-        new = cls.__new__(cls)
-        memo[id(self)] = new
-        import copy
-        for k, v in self.__dict__.items():
-            new.__dict__[k] = {} if k == "last" else copy.deepcopy(v, memo)     # `last` holds a call's graph, not state
-        return new
+    __deepcopy__ = deepcopy_without_last
 
     def head_features(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(staff_x [B, H], voice_x [B, H], class logits [B, 15 + 35] side by side) of an embedding x [B, H]."""

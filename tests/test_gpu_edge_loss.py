@@ -322,6 +322,49 @@ def test_full_table_of_relations_and_grouping_of_the_cross_entropy():
                 lo += n
 
 
+def test_more_tiles_than_the_final_pass_has_lanes():
+    """256 * 64 + 1 edges in one relation are 257 tiles of the cross entropy: lane 0 of the final pass adds tiles 0 and 256 before
+    the tree in LDS (every other case here has at most 5 tiles).  Loss, 1 / alive and the five counts against torch in float64; the
+    small relation behind it in the table gives the bits it gives alone."""
+    from analysisgnn_amd.edge_loss import _EdgeCE, edge_plan
+    H = 4
+
+    def run(rel, y, lab):
+        plan = edge_plan({et(f"r{i}"): (s.to(DEV), d.to(DEV)) for i, (s, d) in enumerate(rel)}, LIMIT, N, select=False)
+        info = {"edge_labels": lab.to(DEV)}
+        total, logit = _EdgeCE.apply(plan, info, 0.1, y.float().to(DEV), w4.float().to(DEV), b4.float().to(DEV))
+        torch.cuda.synchronize()
+        return total.cpu(), logit.cpu(), info["losses"].cpu(), info["inv_cnt"].cpu(), info["counts"].cpu()
+
+    g = torch.Generator().manual_seed(90)
+    rel = [random_edges(256 * 64 + 1, 91), random_edges(70, 92)]
+    E = sum(s.numel() for s, _ in rel)
+    y = torch.randn(E, H, generator=g, dtype=torch.float64)
+    w4 = torch.randn(2, H, generator=g, dtype=torch.float64) * H ** -0.5
+    b4 = torch.randn(2, generator=g, dtype=torch.float64) * 0.1
+    lab = torch.randint(0, 2, (E,), generator=g).to(torch.uint8)
+    total, logit, losses, inv_cnt, counts = run(rel, y, lab)
+    z = y @ w4.t() + b4
+    ce = torch.nn.CrossEntropyLoss(label_smoothing=0.1)
+    ref_losses, lo = [], 0
+    for i, (s, d) in enumerate(rel):
+        a = R.alive_mask(s, d, LIMIT)
+        zi, li = z[lo:lo + s.numel()], lab[lo:lo + s.numel()].long()
+        assert int(a.sum()) > 0 and float((zi[a][:, 1] - zi[a][:, 0]).abs().min()) > 1e-4, "choose another seed"
+        ref_losses.append(ce(zi[a], li[a]))
+        assert bool(torch.isfinite(ref_losses[-1]))
+        assert bool(a[-1]), "the last edge (alone in tile 256 of relation 0) must be alive: leaving its tile out must move the counts"
+        assert counts[i].tolist() == R.confusion(zi, li, a), f"relation {i}: counts"
+        assert float(inv_cnt[i]) == pytest.approx(1.0 / int(a.sum()), rel=1e-6, abs=0.0)
+        lo += s.numel()
+    assert_close_rel(losses, torch.stack(ref_losses), TOL, "losses")
+    assert_close_rel(total, sum(ref_losses) / 2, TOL, "total")
+    n0 = rel[0][0].numel()
+    alone = run([rel[1]], y[n0:], lab[n0:])
+    assert torch.equal(alone[1], logit[n0:]) and torch.equal(alone[2][0], losses[1]) and torch.equal(alone[3][0], inv_cnt[1])
+    assert torch.equal(alone[4][0], counts[1])
+
+
 def test_empty_relations():
     """A relation without an alive edge: loss 0, zero gradient blocks, count 0, and the total stays finite — it is still one of
     the R relations the mean is taken over."""

@@ -149,6 +149,29 @@ def test_a_full_table_of_tasks():
     check(tasks, w, run_hip(tasks, w), reference(tasks, w))
 
 
+def test_more_tiles_than_the_final_pass_has_lanes():
+    """256 * 64 + 1 candidates in one task are 257 tiles: lane 0 of the final pass adds tiles 0 and 256 before the tree in LDS (every
+    other case here has at most 5 tiles).  Tile 256 holds one candidate, the last: it is made a true edge below the limit, so a
+    pass that left that tile out would lose one alive candidate and one of tp / fn.  Loss, 1 / alive and the five counts against
+    float64; the small task behind it in the table gives the bits it gives alone."""
+    H = 4
+    c0, t0 = random_graph(256 * 64 + 1, 77)
+    c0[:, -1] = torch.tensor([5, 7])
+    t0 = torch.cat([t0, c0[:, -1:]], dim=1).contiguous()
+    c1, t1 = random_graph(70, 78)
+    tasks = [(feats(N, H, 79), c0, t0, LIMIT), (feats(N, H, 80), c1, t1, N)]
+    w = [1.0, 0.5]
+    ref = reference(tasks, w)
+    assert all(int(r[2].sum()) > 0 and bool(torch.isfinite(r[3])) for r in ref) and int(ref[0][2].sum()) > 256 * 32
+    assert bool(ref[0][2][-1]) and bool(ref[0][1][-1]), "the one candidate of tile 256 must be alive and labelled positive"
+    both = run_hip(tasks, w)
+    check(tasks, w, both, ref)
+    alone = run_hip([tasks[1]], [w[1]])
+    assert torch.equal(alone[0][0], both[0][1]) and torch.equal(alone[1]["inv_cnt"][0], both[1]["inv_cnt"][1])
+    assert torch.equal(alone[1]["counts"][0], both[1]["counts"][1]) and torch.equal(alone[1]["logits"][0], both[1]["logits"][1])
+    assert torch.equal(alone[2][0], both[2][1])
+
+
 def test_a_task_without_an_alive_candidate_gives_zero():
     H = 64
     cand = torch.tensor([[33, 34, 2], [1, 35, 39]], dtype=torch.int64)        # every candidate has an end at or above the limit
