@@ -40,6 +40,9 @@
  *                         BCEWithLogitsLoss, pair membership and the index_add_ backward (ref: models/analysis.py:397-401, :704-731)
  *   agnn_edge_*           `EdgeDecoder` and the edge-consistency term of the continual trainer: pair features with in-kernel
  *                         dropout, edge labels, the two-class cross entropy (ref: models/analysis.py:805-836, :986-1019)
+ *   agnn_colnorm_*        `activation -> BatchNorm1d -> Dropout` over the row axis (ref: models/chord.py:569-570, core/mlp.py:27-35)
+ *   agnn_onset_pool_*     `OnsetEdgePoolingVersion2`: scatter-mean over onset neighbours and self, selected rows only
+ *                         (ref: models/chord.py:284-287)
  *
  * Conventions (all entry points)
  *   - plain pointers and sizes only; every `const T*`/`T*` marked (device) is device memory owned
@@ -1387,6 +1390,61 @@ typedef struct {
 } agnn_note_features_t;
 size_t agnn_note_features_workspace_bytes(int64_t n_notes, int32_t n_scores, int32_t feature_set);
 int agnn_note_features_f32(const agnn_note_features_t* f /* (host) */, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Column-statistics block (csrc/colnorm.hip):  y = dropout_p( BatchNorm1d( act(x) ) )  over the ROWS of x [n, C] fp32 (row stride
+ * ld_x), act = ReLU (AGNN_CN_RELU) or identity: `layernorm1/2` of the reference's MetricalChordEncoder (models/chord.py:569-570,
+ * BatchNorm1d despite the name) and the body of core/mlp.py's MLP (:27-35).  The statistics are per column, so one call serves
+ * the stacked [n, T * hidden] matrix of T task heads.
+ *   AGNN_CN_TRAIN  batch statistics: workgroups own slabs of AGNN_CN_SLAB rows x 64 columns (16 float4 lanes along the columns,
+ *                  16 lanes down the rows); a slab leaves (mean, M2) of act(x) - K per column, K = act(x[0, column]) (the shift:
+ *                  the variance is never formed as E[a^2] - mean^2), and a final pass joins the slabs' (count, mean, M2) triples
+ *                  pairwise in a fixed order (Chan et al.).  It writes stats and updates running_mean / running_var (unbiased
+ *                  variance, `momentum`) and *num_batches_tracked += 1 in place, on the device; the three may be NULL together.
+ *                  n == 1: AGNN_EINVAL (torch refuses it too).
+ *   otherwise      running statistics (required), one pass, no reduction.
+ * stats [3, C] (caller-owned, written by every forward call, read by backward): the mean as a sum of two floats (hi, lo: y is
+ * computed as ((a - hi) - lo) * rstd, which keeps a column with |mean| >> std exact) and rstd = 1 / sqrt(biased var + eps).
+ * Dropout as agnn_norm_act_* (the library's one random stream, one counter per float4 = row * C / 4 + column / 4; `rng_used`
+ * receives the (seed, step) drawn from); p == 0 draws nothing.
+ * Backward: dx = relu'(x) * gamma * rstd * (g - sum(g) / n - xhat * sum(g * xhat) / n) with g = dy * mask (without
+ * AGNN_CN_TRAIN: gamma * rstd * g), dgamma = sum g * xhat, dbeta = sum g: slabs leave partial column sums, a second launch adds
+ * them in slab order (the scheme of agnn_norm_act_colsum_f32), a third writes dx.  No float atomics: two runs give the same bits.
+ * C % 4 == 0, C >= 4, 16-byte aligned pointers and leading dimensions % 4 == 0 (AGNN_EALIGN), workspace >=
+ * agnn_colnorm_workspace_bytes(n, C) (AGNN_ENOMEM).  n == 0: AGNN_OK, no pointer is looked at.  Stream-ordered, no host read.
+ * ------------------------------------------------------------------------------------------ */
+#define AGNN_CN_RELU   1
+#define AGNN_CN_TRAIN  2
+#define AGNN_CN_SLAB   128
+#define AGNN_CN_FINAL_LANES 16
+size_t agnn_colnorm_workspace_bytes(int64_t n, int32_t C);
+int agnn_colnorm_fwd_f32(const float* x, int64_t ld_x, int64_t n, int32_t C, const float* gamma, const float* beta,
+                         float* running_mean, float* running_var, int64_t* num_batches_tracked, float eps, float momentum,
+                         float p, uint32_t flags, const int64_t* rng_state, uint32_t call_id, float* y, int64_t ld_y,
+                         float* stats, int64_t* rng_used, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+int agnn_colnorm_bwd_f32(const float* x, int64_t ld_x, int64_t n, int32_t C, const float* gamma, const float* stats, float p,
+                         uint32_t flags, const int64_t* rng_state, uint32_t call_id, const float* dy, int64_t ld_dy,
+                         float* dx, int64_t ld_dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                         agnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Onset pooling with row selection (csrc/onsetpool.hip; reference OnsetEdgePoolingVersion2, models/chord.py:284-287):
+ *   out[k, 0:H] = ( a[idx[k]] + sum_{e : dst[e] == idx[k]} a[src[e]] ) / (1 + indeg(idx[k])),   k < n_sel
+ * i.e. scatter(mean) of the edge list with one appended self loop per node, of which only the rows idx are computed.  The edge
+ * list comes as the CSR by destination over all n rows (agnn_csr_build: d_rowptr [n + 1], d_col = sources); a self loop in the
+ * list counts once more.  idx (int64) may be unsorted and may repeat.
+ * Backward through the transposed structures: da[j] = w(j) G(j) + sum_{e : src[e] == j} w(dst[e]) G(dst[e]), w(r) = 1 /
+ * (1 + indeg(r)), G(r) = sum_{k : idx[k] == r} g[k] — s_rowptr / s_col: the CSR by source; sel_rowptr / sel_k: the CSR of idx by
+ * node (row = idx[k], col = k).  Every sum runs in CSR order: no atomics, the same bits every run; every row of da is written.
+ * A group of 4 .. 64 lanes owns a row.  An idx entry or an edge end outside [0, n) contributes nothing and adds 1 to *status
+ * (device int32, may be NULL).  H % 4 == 0, H >= 4, n and n_sel < 2^31: AGNN_EINVAL; alignment as above: AGNN_EALIGN.
+ * n_sel == 0 (forward) / n == 0 (backward): AGNN_OK, no pointer is looked at.
+ * ------------------------------------------------------------------------------------------ */
+int agnn_onset_pool_fwd_f32(const float* a, int64_t ld_a, int64_t n, int32_t H, const int32_t* d_rowptr, const int32_t* d_col,
+                            const int64_t* idx, int64_t n_sel, float* out, int64_t ld_out, int32_t* status, agnn_stream_t stream);
+int agnn_onset_pool_bwd_f32(const float* g, int64_t ld_g, int64_t n_sel, int32_t H, int64_t n, const int32_t* d_rowptr,
+                            const int32_t* s_rowptr, const int32_t* s_col, const int32_t* sel_rowptr, const int32_t* sel_k,
+                            float* da, int64_t ld_da, agnn_stream_t stream);
 
 #ifdef __cplusplus
 }
