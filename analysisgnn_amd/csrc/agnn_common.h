@@ -39,6 +39,33 @@ inline unsigned grid_for(int64_t n_rows) { return static_cast<unsigned>((((n_row
 // zeros, with a finite loss, and only show as non-finite GRADIENTS — seen in round 3 when an un-normalised stack overflowed)
 __device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+// float4 arithmetic, component by component, in place: a += w * v, a += v, a *= s, a /= d (a true division, as torch_scatter's
+// out.div_(count)) ...
+__device__ __forceinline__ void f4_fma(float4& a, float w, const float4& v) {
+  a.x = fmaf(w, v.x, a.x);
+  a.y = fmaf(w, v.y, a.y);
+  a.z = fmaf(w, v.z, a.z);
+  a.w = fmaf(w, v.w, a.w);
+}
+__device__ __forceinline__ void f4_add(float4& a, const float4& v) {
+  a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+}
+__device__ __forceinline__ void f4_scale(float4& a, float s) {
+  a.x *= s; a.y *= s; a.z *= s; a.w *= s;
+}
+__device__ __forceinline__ void f4_div(float4& a, float d) {
+  a.x /= d; a.y /= d; a.z /= d; a.w /= d;
+}
+// ... and by value: s += v (where the in-place form, whose second operand is a reference, compiles differently:
+// profiles/rowwave_isa_identity.md), w * v + a of three float4, and v or zeros by a select (not a multiply by zero: a non-finite
+// value must not leak)
+__device__ __forceinline__ void acc4(float4& s, const float4 v) { s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+__device__ __forceinline__ float4 f4_madd(float4 w, float4 v, float4 a) {
+  return make_float4(fmaf(w.x, v.x, a.x), fmaf(w.y, v.y, a.y), fmaf(w.z, v.z, a.z), fmaf(w.w, v.w, a.w));
+}
+__device__ __forceinline__ float4 f4_keep(bool keep, const float4& v) {
+  return make_float4(keep ? v.x : 0.f, keep ? v.y : 0.f, keep ? v.z : 0.f, keep ? v.w : 0.f);
+}
 
 // MFMA vocabulary: native vectors (operands, accumulators; a staging copy of one is a register move, where a float4 struct copy
 // can become a memcpy through scratch), and the C/D layout of the 32 x 32 tile: lane l, register r -> row d_row32(r, l >> 5),

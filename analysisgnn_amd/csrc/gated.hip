@@ -7,9 +7,11 @@
 // db_j and dh_j.  CSR order, no atomics, bitwise reproducible.  Gather-bound fp32 work; no MFMA.
 #include <cmath>
 
-#include "agnn_common.h"
+#include "rowwave.h"
 
 namespace {
+
+using namespace agnn;
 
 // expf (not __expf) and an IEEE divide: deliberately not the sigmoids of lstm.hip / gru.hip (they differ numerically; do not merge)
 __device__ __forceinline__ float sig(float x) { return 1.f / (1.f + expf(-x)); }
@@ -32,16 +34,16 @@ struct GatedArgs {
 template <int CH>
 __global__ __launch_bounds__(256) void k_gated_fwd(GatedArgs g, float* __restrict__ out, int64_t ld_out) {
   const int lane = threadIdx.x & 63;
-  const int row = ((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) * 4 + (threadIdx.x >> 6);
+  const int row = wave_row<false>();
   if (row >= g.n_rows) return;
   bool on[CH];
   float4 av[CH], acc[CH];
-  const float4* ap = reinterpret_cast<const float4*>(g.a + static_cast<int64_t>(row) * g.ld);
+  const float* ap = g.a + static_cast<int64_t>(row) * g.ld;
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
-    on[k] = (k * 256 + lane * 4) < g.H;
-    av[k] = on[k] ? ap[k * 64 + lane] : agnn::f4_zero();
-    acc[k] = agnn::f4_zero();
+    on[k] = chunk_on(k, lane, g.H);
+    av[k] = chunk_load(ap, k, lane, on[k]);
+    acc[k] = f4_zero();
   }
   const int start = g.rowptr[row], end = g.rowptr[row + 1];
   for (int p = start; p < end; ++p) {
@@ -54,16 +56,15 @@ __global__ __launch_bounds__(256) void k_gated_fwd(GatedArgs g, float* __restric
     for (int k = 0; k < CH; ++k) {
       if (!on[k]) continue;
       const float4 bv = bp[k * 64 + lane], hv = hp[k * 64 + lane];
-      const float4 cv = cp ? cp[k * 64 + lane] : agnn::f4_zero();
+      const float4 cv = cp ? cp[k * 64 + lane] : f4_zero();
       const float4 z = sig4(av[k], bv, cv);
-      acc[k].x = fmaf(z.x, hv.x, acc[k].x); acc[k].y = fmaf(z.y, hv.y, acc[k].y);
-      acc[k].z = fmaf(z.z, hv.z, acc[k].z); acc[k].w = fmaf(z.w, hv.w, acc[k].w);
+      acc[k] = f4_madd(z, hv, acc[k]);
     }
   }
-  float4* op = reinterpret_cast<float4*>(out + static_cast<int64_t>(row) * ld_out);
+  float* op = out + static_cast<int64_t>(row) * ld_out;
 #pragma unroll
   for (int k = 0; k < CH; ++k)
-    if (on[k]) op[k * 64 + lane] = acc[k];
+    if (on[k]) chunk_store(op, k, lane, acc[k]);
 }
 
 // by destination: da_i = sum_e dS_i * h_j * z(1-z); optional dc[perm[p]] = that summand
@@ -71,18 +72,18 @@ template <int CH>
 __global__ __launch_bounds__(256) void k_gated_bwd_dst(GatedArgs g, const float* __restrict__ ds, int64_t ld_ds,
                                                        float* __restrict__ da, float* __restrict__ dc) {
   const int lane = threadIdx.x & 63;
-  const int row = ((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) * 4 + (threadIdx.x >> 6);
+  const int row = wave_row<false>();
   if (row >= g.n_rows) return;
   bool on[CH];
   float4 av[CH], dv[CH], acc[CH];
-  const float4* ap = reinterpret_cast<const float4*>(g.a + static_cast<int64_t>(row) * g.ld);
-  const float4* dp = reinterpret_cast<const float4*>(ds + static_cast<int64_t>(row) * ld_ds);
+  const float* ap = g.a + static_cast<int64_t>(row) * g.ld;
+  const float* dp = ds + static_cast<int64_t>(row) * ld_ds;
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
-    on[k] = (k * 256 + lane * 4) < g.H;
-    av[k] = on[k] ? ap[k * 64 + lane] : agnn::f4_zero();
-    dv[k] = on[k] ? dp[k * 64 + lane] : agnn::f4_zero();
-    acc[k] = agnn::f4_zero();
+    on[k] = chunk_on(k, lane, g.H);
+    av[k] = chunk_load(ap, k, lane, on[k]);
+    dv[k] = chunk_load(dp, k, lane, on[k]);
+    acc[k] = f4_zero();
   }
   const int start = g.rowptr[row], end = g.rowptr[row + 1];
   for (int p = start; p < end; ++p) {
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(256) void k_gated_bwd_dst(GatedArgs g, const float*
     for (int k = 0; k < CH; ++k) {
       if (!on[k]) continue;
       const float4 bv = bp[k * 64 + lane], hv = hp[k * 64 + lane];
-      const float4 cv = cp ? cp[k * 64 + lane] : agnn::f4_zero();
+      const float4 cv = cp ? cp[k * 64 + lane] : f4_zero();
       const float4 z = sig4(av[k], bv, cv);
       const float4 t = make_float4(dv[k].x * hv.x * z.x * (1.f - z.x), dv[k].y * hv.y * z.y * (1.f - z.y),
                                    dv[k].z * hv.z * z.z * (1.f - z.z), dv[k].w * hv.w * z.w * (1.f - z.w));
@@ -104,10 +105,10 @@ __global__ __launch_bounds__(256) void k_gated_bwd_dst(GatedArgs g, const float*
       if (dcp) dcp[k * 64 + lane] = t;
     }
   }
-  float4* op = reinterpret_cast<float4*>(da + static_cast<int64_t>(row) * g.ld);
+  float* op = da + static_cast<int64_t>(row) * g.ld;
 #pragma unroll
   for (int k = 0; k < CH; ++k)
-    if (on[k]) op[k * 64 + lane] = acc[k];
+    if (on[k]) chunk_store(op, k, lane, acc[k]);
 }
 
 // by source (transposed CSR: row = source j, col = destination i):
@@ -116,19 +117,19 @@ template <int CH>
 __global__ __launch_bounds__(256) void k_gated_bwd_src(GatedArgs g, const float* __restrict__ ds, int64_t ld_ds,
                                                        float* __restrict__ db, float* __restrict__ dh) {
   const int lane = threadIdx.x & 63;
-  const int row = ((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) * 4 + (threadIdx.x >> 6);
+  const int row = wave_row<false>();
   if (row >= g.n_rows) return;
   bool on[CH];
   float4 bv[CH], hv[CH], accb[CH], acch[CH];
-  const float4* bp = reinterpret_cast<const float4*>(g.b + static_cast<int64_t>(row) * g.ld);
-  const float4* hp = reinterpret_cast<const float4*>(g.h + static_cast<int64_t>(row) * g.ld);
+  const float* bp = g.b + static_cast<int64_t>(row) * g.ld;
+  const float* hp = g.h + static_cast<int64_t>(row) * g.ld;
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
-    on[k] = (k * 256 + lane * 4) < g.H;
-    bv[k] = on[k] ? bp[k * 64 + lane] : agnn::f4_zero();
-    hv[k] = on[k] ? hp[k * 64 + lane] : agnn::f4_zero();
-    accb[k] = agnn::f4_zero();
-    acch[k] = agnn::f4_zero();
+    on[k] = chunk_on(k, lane, g.H);
+    bv[k] = chunk_load(bp, k, lane, on[k]);
+    hv[k] = chunk_load(hp, k, lane, on[k]);
+    accb[k] = f4_zero();
+    acch[k] = f4_zero();
   }
   const int start = g.rowptr[row], end = g.rowptr[row + 1];
   for (int p = start; p < end; ++p) {
@@ -141,10 +142,9 @@ __global__ __launch_bounds__(256) void k_gated_bwd_src(GatedArgs g, const float*
     for (int k = 0; k < CH; ++k) {
       if (!on[k]) continue;
       const float4 av = ap[k * 64 + lane], dv = dp[k * 64 + lane];
-      const float4 cv = cp ? cp[k * 64 + lane] : agnn::f4_zero();
+      const float4 cv = cp ? cp[k * 64 + lane] : f4_zero();
       const float4 z = sig4(av, bv[k], cv);
-      acch[k].x = fmaf(z.x, dv.x, acch[k].x); acch[k].y = fmaf(z.y, dv.y, acch[k].y);
-      acch[k].z = fmaf(z.z, dv.z, acch[k].z); acch[k].w = fmaf(z.w, dv.w, acch[k].w);
+      acch[k] = f4_madd(z, dv, acch[k]);
       accb[k].x += dv.x * hv[k].x * z.x * (1.f - z.x); accb[k].y += dv.y * hv[k].y * z.y * (1.f - z.y);
       accb[k].z += dv.z * hv[k].z * z.z * (1.f - z.z); accb[k].w += dv.w * hv[k].w * z.w * (1.f - z.w);
     }
@@ -160,55 +160,43 @@ __global__ __launch_bounds__(256) void k_gated_bwd_src(GatedArgs g, const float*
 }
 
 int gated_check(const char* who, const agnn_gated_t* g) {
-  using namespace agnn;
   if (!g) return fail(AGNN_EINVAL, "%s: null descriptor", who);
-  if (g->n_rows < 0 || g->n_rows >= (int64_t{1} << 31)) return fail(AGNN_EINVAL, "%s: n_rows=%lld", who, (long long)g->n_rows);
-  if (g->H <= 0 || (g->H & 3) || g->H > 1024) return fail(AGNN_EINVAL, "%s: H=%d must be a multiple of 4 in [4,1024]", who, g->H);
-  if (g->n_rows == 0) return 1;
+  if (int rc = check_wave_rows(who, g->n_rows, g->H)) return rc;
   if (!g->rowptr || !g->col || !g->a || !g->b || !g->h) return fail(AGNN_EINVAL, "%s: null argument", who);
   if (!aligned16(g->a) || !aligned16(g->b) || !aligned16(g->h) || (g->ld & 3) || g->ld < g->H) return fail(AGNN_EALIGN, "%s: a/b/h misaligned or ld < H", who);
-  if (g->c && (!aligned16(g->c) || (g->ld_c & 3) || g->ld_c < g->H || !g->perm)) return fail(AGNN_EALIGN, "%s: per-edge term misaligned or perm missing", who);
+  if (g->c && (!f4_rows(g->c, g->ld_c, g->H) || !g->perm)) return fail(AGNN_EALIGN, "%s: per-edge term misaligned or perm missing", who);
   return 0;
 }
 
-inline GatedArgs to_args(const agnn_gated_t* g) {
-  return GatedArgs{g->rowptr, g->col, g->perm, g->a, g->b, g->h, g->c, g->ld, g->ld_c, static_cast<int32_t>(g->n_rows), g->H};
+// the kernel instantiation for the descriptor's width, on the grid of its rows
+template <typename F>
+void gated_launch(const agnn_gated_t* g, agnn_stream_t stream_, F&& launch) {
+  const GatedArgs a{g->rowptr, g->col, g->perm, g->a, g->b, g->h, g->c, g->ld, g->ld_c, static_cast<int32_t>(g->n_rows), g->H};
+  for_width(g->H, [&](auto ch) { launch(ch, dim3(grid_for(g->n_rows)), static_cast<hipStream_t>(stream_), a); });
 }
-
-#define AGNN_GATED_LAUNCH(KERN, ...)                                                                          \
-  do {                                                                                                        \
-    const dim3 grid(agnn::grid_for(g->n_rows)), block(256);                                                            \
-    hipStream_t s = static_cast<hipStream_t>(stream_);                                                        \
-    if (g->H <= 256) hipLaunchKernelGGL(KERN<1>, grid, block, 0, s, to_args(g), __VA_ARGS__);                 \
-    else if (g->H <= 512) hipLaunchKernelGGL(KERN<2>, grid, block, 0, s, to_args(g), __VA_ARGS__);            \
-    else hipLaunchKernelGGL(KERN<4>, grid, block, 0, s, to_args(g), __VA_ARGS__);                             \
-  } while (0)
 
 }  // namespace
 
 extern "C" int agnn_gated_fwd_f32(const agnn_gated_t* g, float* out, int64_t ld_out, agnn_stream_t stream_) {
-  using namespace agnn;
   if (int rc = gated_check("gated_fwd", g)) return rc > 0 ? AGNN_OK : rc;
-  if (!out || !aligned16(out) || (ld_out & 3) || ld_out < g->H) return fail(AGNN_EALIGN, "gated_fwd: out misaligned or ld_out < H");
-  AGNN_GATED_LAUNCH(k_gated_fwd, out, ld_out);
+  if (!out || !f4_rows(out, ld_out, g->H)) return fail(AGNN_EALIGN, "gated_fwd: out misaligned or ld_out < H");
+  gated_launch(g, stream_, [&](auto ch, dim3 grid, hipStream_t s, const GatedArgs& a) { hipLaunchKernelGGL(k_gated_fwd<decltype(ch)::value>, grid, dim3(256), 0, s, a, out, ld_out); });
   return check_launch("gated_fwd");
 }
 
 extern "C" int agnn_gated_bwd_dst_f32(const agnn_gated_t* g, const float* ds, int64_t ld_ds, float* da, float* dc,
                                       agnn_stream_t stream_) {
-  using namespace agnn;
   if (int rc = gated_check("gated_bwd_dst", g)) return rc > 0 ? AGNN_OK : rc;
   if (!ds || !da || !aligned16(ds) || !aligned16(da) || (ld_ds & 3) || ld_ds < g->H || !g->perm) return fail(AGNN_EALIGN, "gated_bwd_dst: ds/da misaligned, ld_ds < H or perm missing");
   if (dc && (!g->c || !aligned16(dc))) return fail(AGNN_EALIGN, "gated_bwd_dst: dc misaligned or given without the per-edge term c (dc shares ld_c)");
-  AGNN_GATED_LAUNCH(k_gated_bwd_dst, ds, ld_ds, da, dc);
+  gated_launch(g, stream_, [&](auto ch, dim3 grid, hipStream_t s, const GatedArgs& a) { hipLaunchKernelGGL(k_gated_bwd_dst<decltype(ch)::value>, grid, dim3(256), 0, s, a, ds, ld_ds, da, dc); });
   return check_launch("gated_bwd_dst");
 }
 
 extern "C" int agnn_gated_bwd_src_f32(const agnn_gated_t* g, const float* ds, int64_t ld_ds, float* db, float* dh,
                                       agnn_stream_t stream_) {
-  using namespace agnn;
   if (int rc = gated_check("gated_bwd_src", g)) return rc > 0 ? AGNN_OK : rc;
   if (!ds || !db || !dh || !aligned16(ds) || !aligned16(db) || !aligned16(dh) || (ld_ds & 3) || ld_ds < g->H || !g->perm) return fail(AGNN_EALIGN, "gated_bwd_src: misaligned, ld_ds < H or perm missing");
-  AGNN_GATED_LAUNCH(k_gated_bwd_src, ds, ld_ds, db, dh);
+  gated_launch(g, stream_, [&](auto ch, dim3 grid, hipStream_t s, const GatedArgs& a) { hipLaunchKernelGGL(k_gated_bwd_src<decltype(ch)::value>, grid, dim3(256), 0, s, a, ds, ld_ds, db, dh); });
   return check_launch("gated_bwd_src");
 }

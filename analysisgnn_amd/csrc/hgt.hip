@@ -19,7 +19,7 @@
 // HBM/L2-bound gather work; no MFMA here.
 #include <cmath>
 
-#include "agnn_common.h"
+#include "rowwave.h"
 
 namespace {
 
@@ -57,9 +57,7 @@ template <int CH>
 __device__ __forceinline__ void hgt_fwd_rows(const HgtTable& t, int r0, int r1, const HgtArgs& a, float* __restrict__ out, int64_t ld_out,
                                              float* __restrict__ m_out, float* __restrict__ linv_out, int block, int n_blocks) {
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int vb = (block & 7) * (n_blocks >> 3) + (block >> 3);   // XCD-contiguous row slabs
-  const int row = vb * 4 + wave;
+  const int row = agnn::wave_row<true>(block, n_blocks);
   if (row >= a.n_rows) return;
   const int D = a.H / a.heads;
   const int gl = D >> 2;
@@ -71,7 +69,7 @@ __device__ __forceinline__ void hgt_fwd_rows(const HgtTable& t, int r0, int r1, 
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     const int f = c * 256 + lane * 4;
-    on[c] = f < a.H;
+    on[c] = agnn::chunk_on(c, lane, a.H);
     head[c] = on[c] ? f / D : 0;
     qv[c] = on[c] ? qp[c * 64 + lane] : agnn::f4_zero();
     acc[c] = agnn::f4_zero();
@@ -177,9 +175,7 @@ __global__ __launch_bounds__(256) void k_hgt_bwd_dst(HgtTable t, HgtArgs a, cons
                                                      const float* __restrict__ m_in, const float* __restrict__ linv_in,
                                                      float* __restrict__ dq, int64_t ld_dq) {
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int vb = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  const int row = vb * 4 + wave;
+  const int row = agnn::wave_row<true>();
   if (row >= a.n_rows) return;
   const int D = a.H / a.heads;
   const int gl = D >> 2;
@@ -193,7 +189,7 @@ __global__ __launch_bounds__(256) void k_hgt_bwd_dst(HgtTable t, HgtArgs a, cons
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     const int f = c * 256 + lane * 4;
-    on[c] = f < a.H;
+    on[c] = agnn::chunk_on(c, lane, a.H);
     head[c] = on[c] ? f / D : 0;
     lead[c] = on[c] && (f % D) == 0;
     qv[c] = on[c] ? qp[c * 64 + lane] : agnn::f4_zero();
@@ -277,9 +273,7 @@ __device__ __forceinline__ void hgt_bwd_src_rows(const int32_t* __restrict__ row
                                                  const float* __restrict__ dm, int64_t ld_dm, float* __restrict__ dk,
                                                  float* __restrict__ dv, int64_t ld_o, const int block, const int n_blocks) {
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int vb = (block & 7) * (n_blocks >> 3) + (block >> 3);
-  const int row = vb * 4 + wave;
+  const int row = agnn::wave_row<true>(block, n_blocks);
   if (row >= a.n_rows) return;
   const int D = a.H / a.heads;
   bool on[CH];
@@ -288,7 +282,7 @@ __device__ __forceinline__ void hgt_bwd_src_rows(const int32_t* __restrict__ row
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     const int f = c * 256 + lane * 4;
-    on[c] = f < a.H;
+    on[c] = agnn::chunk_on(c, lane, a.H);
     head[c] = on[c] ? f / D : 0;
     dka[c] = agnn::f4_zero();
     dva[c] = agnn::f4_zero();
@@ -357,8 +351,7 @@ __global__ __launch_bounds__(256) void k_hgt_bwd_src_batch(SrcBatch b) {
 
 int check_shape(const char* who, int64_t n_rows, int32_t H, int32_t heads) {
   using namespace agnn;
-  if (n_rows < 0 || n_rows >= (int64_t{1} << 31)) return fail(AGNN_EINVAL, "%s: n_rows=%lld", who, (long long)n_rows);
-  if (H <= 0 || (H & 3) || H > 1024) return fail(AGNN_EINVAL, "%s: H=%d must be a multiple of 4 in [4,1024]", who, H);
+  if (int rc = check_wave_rows(who, n_rows, H); rc < 0) return rc;      // no row: the callers still look at the rest
   if (heads <= 0 || H % heads) return fail(AGNN_EINVAL, "%s: heads=%d must divide H=%d", who, heads, H);
   const int D = H / heads;
   const int gl = D / 4;
@@ -389,9 +382,7 @@ extern "C" int agnn_hgt_attn_fwd_f32(int n_rel, const agnn_hgt_rel_t* rels, cons
   HgtArgs a{q, ld_q, static_cast<int32_t>(n_rows), H, heads, INT32_MAX};
   hipStream_t s = static_cast<hipStream_t>(stream_);
   const dim3 grid(agnn::grid_for(n_rows)), block(256);
-  if (H <= 256) hipLaunchKernelGGL(k_hgt_fwd<1>, grid, block, 0, s, t, a, out, ld_out, m_out, linv_out);
-  else if (H <= 512) hipLaunchKernelGGL(k_hgt_fwd<2>, grid, block, 0, s, t, a, out, ld_out, m_out, linv_out);
-  else hipLaunchKernelGGL(k_hgt_fwd<4>, grid, block, 0, s, t, a, out, ld_out, m_out, linv_out);
+  for_width(H, [&](auto ch) { hipLaunchKernelGGL(k_hgt_fwd<decltype(ch)::value>, grid, block, 0, s, t, a, out, ld_out, m_out, linv_out); });
   return check_launch("hgt_fwd");
 }
 
@@ -426,9 +417,7 @@ extern "C" int agnn_hgt_attn_fwd_multi_f32(int32_t n_items, const agnn_hgt_dst_i
   t.n_rel = nr;
   hipStream_t s = static_cast<hipStream_t>(stream_);
   const dim3 grid(static_cast<unsigned>(blocks)), block(256);
-  if (H <= 256) hipLaunchKernelGGL(k_hgt_fwd_multi<1>, grid, block, 0, s, t, mm);
-  else if (H <= 512) hipLaunchKernelGGL(k_hgt_fwd_multi<2>, grid, block, 0, s, t, mm);
-  else hipLaunchKernelGGL(k_hgt_fwd_multi<4>, grid, block, 0, s, t, mm);
+  for_width(H, [&](auto ch) { hipLaunchKernelGGL(k_hgt_fwd_multi<decltype(ch)::value>, grid, block, 0, s, t, mm); });
   return check_launch("hgt_fwd_multi");
 }
 
@@ -453,9 +442,7 @@ extern "C" int agnn_hgt_attn_bwd_dst_f32(int n_rel, const agnn_hgt_rel_t* rels, 
   HgtArgs a{q, ld_q, static_cast<int32_t>(n_rows), H, heads, INT32_MAX};
   hipStream_t s = static_cast<hipStream_t>(stream_);
   const dim3 grid(agnn::grid_for(n_rows)), block(256);
-  if (H <= 256) hipLaunchKernelGGL(k_hgt_bwd_dst<1>, grid, block, 0, s, t, a, dm, ld_dm, out, ld_out, m_in, linv_in, dq, ld_dq);
-  else if (H <= 512) hipLaunchKernelGGL(k_hgt_bwd_dst<2>, grid, block, 0, s, t, a, dm, ld_dm, out, ld_out, m_in, linv_in, dq, ld_dq);
-  else hipLaunchKernelGGL(k_hgt_bwd_dst<4>, grid, block, 0, s, t, a, dm, ld_dm, out, ld_out, m_in, linv_in, dq, ld_dq);
+  for_width(H, [&](auto ch) { hipLaunchKernelGGL(k_hgt_bwd_dst<decltype(ch)::value>, grid, block, 0, s, t, a, dm, ld_dm, out, ld_out, m_in, linv_in, dq, ld_dq); });
   return check_launch("hgt_bwd_dst");
 }
 
@@ -481,8 +468,6 @@ extern "C" int agnn_hgt_attn_bwd_src_batch_f32(int32_t n_items, const agnn_hgt_s
   b.first[b.n] = blocks;
   hipStream_t s = static_cast<hipStream_t>(stream_);
   const dim3 grid(static_cast<unsigned>(blocks)), block(256);
-  if (H <= 256) hipLaunchKernelGGL(k_hgt_bwd_src_batch<1>, grid, block, 0, s, b);
-  else if (H <= 512) hipLaunchKernelGGL(k_hgt_bwd_src_batch<2>, grid, block, 0, s, b);
-  else hipLaunchKernelGGL(k_hgt_bwd_src_batch<4>, grid, block, 0, s, b);
+  for_width(H, [&](auto ch) { hipLaunchKernelGGL(k_hgt_bwd_src_batch<decltype(ch)::value>, grid, block, 0, s, b); });
   return check_launch("hgt_bwd_src_batch");
 }

@@ -25,8 +25,6 @@ struct PoolFwd {
   int32_t* status;
 };
 
-__device__ __forceinline__ void acc4(float4& s, const float4 v) { s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-
 __global__ __launch_bounds__(256) void k_pool_fwd(PoolFwd p, int lg) {
   const agnn::Lanes L = agnn::lanes_of(lg);
   const int64_t k = static_cast<int64_t>(blockIdx.x) * L.gpb + L.grp;
@@ -46,11 +44,12 @@ __global__ __launch_bounds__(256) void k_pool_fwd(PoolFwd p, int lg) {
     for (int e = e0; e < e1; ++e) {
       const int j = p.col[e];
       if (j < 0 || j >= p.n) { ++bad; continue; }
-      acc4(s, reinterpret_cast<const float4*>(p.a + static_cast<int64_t>(j) * p.ld_a)[c4]);
+      agnn::acc4(s, reinterpret_cast<const float4*>(p.a + static_cast<int64_t>(j) * p.ld_a)[c4]);
       ++deg;
     }
     const float w = 1.f / static_cast<float>(1 + deg);
-    reinterpret_cast<float4*>(op)[c4] = make_float4(s.x * w, s.y * w, s.z * w, s.w * w);
+    agnn::f4_scale(s, w);
+    reinterpret_cast<float4*>(op)[c4] = s;
   }
   if (L.lig == 0 && bad && p.status != nullptr) atomicAdd(p.status, 1);
 }
@@ -78,7 +77,7 @@ __device__ __forceinline__ void add_node(const PoolBwd& p, int64_t r, int c4, fl
   for (int q = k0; q < k1; ++q) {
     const int k = p.sel_k[q];
     if (k < 0 || k >= p.n_sel) continue;
-    acc4(t, reinterpret_cast<const float4*>(p.g + static_cast<int64_t>(k) * p.ld_g)[c4]);
+    agnn::acc4(t, reinterpret_cast<const float4*>(p.g + static_cast<int64_t>(k) * p.ld_g)[c4]);
   }
   const float w = 1.f / static_cast<float>(1 + (p.d_rowptr[r + 1] - p.d_rowptr[r]));
   s.x = fmaf(t.x, w, s.x); s.y = fmaf(t.y, w, s.y); s.z = fmaf(t.z, w, s.z); s.w = fmaf(t.w, w, s.w);
@@ -109,15 +108,6 @@ int pool_sizes(const char* who, int32_t H, int64_t n, int64_t n_sel) {
   return AGNN_OK;
 }
 
-int pool_rows(const char* who, const char* name, const void* ptr, int64_t ld, int64_t width) {
-  using namespace agnn;
-  if (!ptr) return fail(AGNN_EINVAL, "%s: %s is null", who, name);
-  if (ld < width) return fail(AGNN_EINVAL, "%s: ld_%s=%lld < %lld", who, name, (long long)ld, (long long)width);
-  if (ld & 3) return fail(AGNN_EALIGN, "%s: ld_%s=%lld is not a multiple of 4", who, name, (long long)ld);
-  if (!aligned16(ptr)) return fail(AGNN_EALIGN, "%s: %s is not 16-byte aligned", who, name);
-  return AGNN_OK;
-}
-
 }  // namespace
 
 extern "C" int agnn_onset_pool_fwd_f32(const float* a, int64_t ld_a, int64_t n, int32_t H, const int32_t* d_rowptr, const int32_t* d_col,
@@ -127,8 +117,8 @@ extern "C" int agnn_onset_pool_fwd_f32(const float* a, int64_t ld_a, int64_t n, 
   if (int rc = pool_sizes(who, H, n, n_sel)) return rc;
   if (n_sel == 0) return AGNN_OK;
   if (n == 0) return fail(AGNN_EINVAL, "%s: n_sel=%lld rows selected out of n=0", who, (long long)n_sel);
-  if (int rc = pool_rows(who, "a", a, ld_a, H)) return rc;
-  if (int rc = pool_rows(who, "out", out, ld_out, H)) return rc;
+  if (int rc = check_matrix(who, "a", a, ld_a, H)) return rc;
+  if (int rc = check_matrix(who, "out", out, ld_out, H)) return rc;
   if (!d_rowptr || !d_col || !idx) return fail(AGNN_EINVAL, "%s: d_rowptr, d_col or idx is null", who);
   const int lg = group_log2(H / 4), gpb = 256 >> lg;
   PoolFwd p{a, ld_a, n, H / 4, d_rowptr, d_col, idx, n_sel, out, ld_out, status};
@@ -143,9 +133,9 @@ extern "C" int agnn_onset_pool_bwd_f32(const float* g, int64_t ld_g, int64_t n_s
   const char* who = "onset_pool_bwd";
   if (int rc = pool_sizes(who, H, n, n_sel)) return rc;
   if (n == 0) return AGNN_OK;
-  if (int rc = pool_rows(who, "da", da, ld_da, H)) return rc;
+  if (int rc = check_matrix(who, "da", da, ld_da, H)) return rc;
   if (n_sel > 0) {
-    if (int rc = pool_rows(who, "g", g, ld_g, H)) return rc;
+    if (int rc = check_matrix(who, "g", g, ld_g, H)) return rc;
   }
   if (!d_rowptr || !s_rowptr || !s_col || !sel_rowptr || !sel_k) return fail(AGNN_EINVAL, "%s: an index array is null", who);
   const int lg = group_log2(H / 4), gpb = 256 >> lg;

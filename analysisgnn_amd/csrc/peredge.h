@@ -6,7 +6,7 @@
 #pragma once
 #include <algorithm>
 
-#include "agnn_common.h"
+#include "rowwave.h"
 
 namespace agnn {
 
@@ -168,13 +168,11 @@ inline int check_sizes(const char* who, const char* noun, int i, int64_t E, int6
   return AGNN_OK;
 }
 
-// a [rows, H] float matrix a kernel reads or writes with float4
+// a [rows, H] float matrix a kernel reads or writes with float4: rowwave.h's validator, the segment named in front of the operand
 inline int check_rows(const char* who, const char* noun, int i, const char* name, const void* p, int64_t ld, int32_t H) {
-  if (!p) return fail(AGNN_EINVAL, "%s: %s %d: %s is null", who, noun, i, name);
-  if (ld < H) return fail(AGNN_EINVAL, "%s: %s %d: ld_%s=%lld < H=%d", who, noun, i, name, (long long)ld, H);
-  if (ld % 4 != 0) return fail(AGNN_EALIGN, "%s: %s %d: ld_%s=%lld is not a multiple of 4", who, noun, i, name, (long long)ld);
-  if (!aligned16(p)) return fail(AGNN_EALIGN, "%s: %s %d: %s is not 16-byte aligned", who, noun, i, name);
-  return AGNN_OK;
+  char where[96];
+  snprintf(where, sizeof(where), "%s: %s %d", who, noun, i);
+  return check_matrix(where, name, p, ld, H);
 }
 
 // a grid of `total` workgroups (tiles, slots): `what` names them in the message

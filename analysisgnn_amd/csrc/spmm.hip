@@ -12,7 +12,7 @@
 // (reference analysisgnn/models/core/gnn.py:70-74), the zero-initialised scatter_add calls
 // (core/gnn.py:511,539; core/hgnn.py:406-407), PyG SAGEConv's mean aggregation
 // (models/cadence.py:147-159) and the onset pooling (models/analysis.py:580-586).
-#include "agnn_common.h"
+#include "rowwave.h"
 
 namespace {
 
@@ -47,19 +47,7 @@ struct SpmmArgs {
   const float* self2_scale;
 };
 
-using agnn::f4_zero;
-__device__ __forceinline__ void f4_fma(float4& a, float w, const float4& v) {
-  a.x = fmaf(w, v.x, a.x);
-  a.y = fmaf(w, v.y, a.y);
-  a.z = fmaf(w, v.z, a.z);
-  a.w = fmaf(w, v.w, a.w);
-}
-__device__ __forceinline__ void f4_add(float4& a, const float4& v) {
-  a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-}
-__device__ __forceinline__ void f4_div(float4& a, float d) {  // true division, as torch_scatter's out.div_(count)
-  a.x /= d; a.y /= d; a.z /= d; a.w /= d;
-}
+using namespace agnn;
 
 // ------------------------------------------------------------------------------------------
 // Generic kernel ("scalarised"): one wavefront per output row, and EVERYTHING that is the same for the 64
@@ -76,6 +64,9 @@ typedef const __attribute__((address_space(4))) float* k_f32p;
 template <int CH, bool SHARED, bool SELF>
 __global__ __launch_bounds__(256) void k_spmm_s(RelTable t, SpmmArgs a) {
   const int lane = threadIdx.x & 63;
+  // wave_row<true>() and, below, the per-relation store are written out in this kernel and in k_spmm_fast7: through rowwave.h's
+  // helpers some instantiations get other registers or another order (profiles/rowwave_isa_identity.md), and both kernels keep
+  // the assembly they were measured with
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int vb = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);   // XCD-contiguous row slabs
   const int row = vb * 4 + wave;                                            // wave-uniform (SGPR)
@@ -85,13 +76,13 @@ __global__ __launch_bounds__(256) void k_spmm_s(RelTable t, SpmmArgs a) {
   const bool accum = (a.flags & AGNN_SPMM_ACCUM) != 0;
   bool lane_on[CH];
 #pragma unroll
-  for (int c = 0; c < CH; ++c) lane_on[c] = (c * 256 + lane * 4) < a.H;
+  for (int c = 0; c < CH; ++c) lane_on[c] = chunk_on(c, lane, a.H);
 
   float4 selfv[SELF ? CH : 1];
   if (SELF) {
-    const float4* sp = reinterpret_cast<const float4*>(a.self + static_cast<int64_t>(row) * a.ld_self);
+    const float* sp = a.self + static_cast<int64_t>(row) * a.ld_self;
 #pragma unroll
-    for (int c = 0; c < (SELF ? CH : 1); ++c) selfv[c] = lane_on[c] ? sp[c * 64 + lane] : f4_zero();
+    for (int c = 0; c < (SELF ? CH : 1); ++c) selfv[c] = chunk_load(sp, c, lane, lane_on[c]);
   }
   float4 tot[SHARED ? CH : 1];
 #pragma unroll
@@ -134,9 +125,9 @@ __global__ __launch_bounds__(256) void k_spmm_s(RelTable t, SpmmArgs a) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (ok[u]) {
-          const float4* sp = reinterpret_cast<const float4*>(src + static_cast<int64_t>(ck[u]) * ld);
+          const float* sp = src + static_cast<int64_t>(ck[u]) * ld;
 #pragma unroll
-          for (int c = 0; c < CH; ++c) v[u][c] = lane_on[c] ? sp[c * 64 + lane] : f4_zero();
+          for (int c = 0; c < CH; ++c) v[u][c] = chunk_load(sp, c, lane, lane_on[c]);
         }
       }
 #pragma unroll
@@ -170,169 +161,25 @@ __global__ __launch_bounds__(256) void k_spmm_s(RelTable t, SpmmArgs a) {
     }
   }
   if (SHARED) {
-    float4* op = reinterpret_cast<float4*>(a.out + static_cast<int64_t>(row) * a.ld_out);
+    float* op = a.out + static_cast<int64_t>(row) * a.ld_out;
 #pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      if (!lane_on[c]) continue;
-      float4 o = tot[SHARED ? c : 0];
-      if (accum) f4_add(o, op[c * 64 + lane]);
-      op[c * 64 + lane] = o;
-    }
+    for (int c = 0; c < CH; ++c)
+      if (lane_on[c]) chunk_store(op, c, lane, tot[SHARED ? c : 0], accum);
   }
 }
 
 
 // ------------------------------------------------------------------------------------------
-// Fast path.  PMC on the earlier variants (profiles/r01_spmm_kernel_study.md): ~1000 instructions per row,
-// SQ_ACTIVE_INST_ANY ~ the whole kernel time — the aggregation was INSTRUCTION-ISSUE bound (rows have
-// ~1.6 neighbours per relation), not bandwidth bound.  This kernel spends ~1/4 of the instructions:
-//   * relations are processed four at a time with all four `rowptr` pairs fetched by back-to-back
-//     scalar loads and all four column-id vectors by back-to-back coalesced vector loads, so a row
-//     costs three dependent memory round trips, not 3R;
-//   * column ids / weights of a segment sit in one VGPR each and are broadcast with v_readlane;
-//     neighbour rows are fetched as scalar base + lane offset, two in flight per segment;
-//   * no per-edge predicates: this path is taken only when there is no trimming (rowend), no
-//     per-edge weight, no self-loop / column filter and H is exactly 256 or 512 (host-side check);
-//   * 1/count is one v_rcp_f32 (<= 1 ulp) and four multiplies instead of four IEEE divisions.
-// Everything else falls back to k_spmm_s above (same results up to that ulp).
-// ------------------------------------------------------------------------------------------
-template <int CH, bool HAS_CS, bool SHARED, bool SELF>
-__global__ __launch_bounds__(256) void k_spmm_fast(RelTable t, SpmmArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int vb = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);   // XCD-contiguous row slabs
-  const int row = vb * 4 + wave;
-  if (row >= a.n_rows) return;
-  const bool mean = (a.flags & AGNN_SPMM_MEAN) != 0;
-  const bool accum = (a.flags & AGNN_SPMM_ACCUM) != 0;
-  const uint32_t loff = static_cast<uint32_t>(lane) * 16u;
-
-  float4 selfv[SELF ? CH : 1];
-  if (SELF) {
-    const char* sp = reinterpret_cast<const char*>(a.self + static_cast<int64_t>(row) * a.ld_self);
-#pragma unroll
-    for (int c = 0; c < (SELF ? CH : 1); ++c) selfv[c] = *reinterpret_cast<const float4*>(sp + (loff + c * 1024u));
-  }
-  float4 tot[SHARED ? CH : 1];
-#pragma unroll
-  for (int c = 0; c < (SHARED ? CH : 1); ++c) tot[c] = f4_zero();
-
-  for (int r0 = 0; r0 < t.n_rel; r0 += 4) {
-    int start[4], n[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      start[u] = 0;
-      n[u] = 0;
-      if (r0 + u < t.n_rel) {
-        const k_i32p rp = (k_i32p)t.r[r0 + u].rowptr;
-        start[u] = rp[row];
-        n[u] = rp[row + 1] - start[u];
-      }
-    }
-    int colv[4];
-    float wv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      colv[u] = 0;
-      if (n[u] > 0 && lane < n[u]) colv[u] = t.r[r0 + u].col[start[u] + lane];
-    }
-    if (HAS_CS) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        wv[u] = 0.f;
-        if (n[u] > 0 && lane < n[u]) wv[u] = t.r[r0 + u].colscale[colv[u]];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (r0 + u >= t.n_rel) break;
-      const agnn_rel_t& R = t.r[r0 + u];
-      const char* src = reinterpret_cast<const char*>(R.src);
-      const int64_t ldb = R.ld_src * 4;
-      float4 acc[CH];
-#pragma unroll
-      for (int c = 0; c < CH; ++c) acc[c] = f4_zero();
-      const int nn = n[u];
-      for (int base = 0; base < nn; base += 64) {
-        int cv = colv[u];
-        float wq = HAS_CS ? wv[u] : 1.f;
-        if (base > 0) {                       // rows with more than 64 neighbours: next batch of ids
-          cv = 0;
-          wq = 0.f;
-          if (lane < nn - base) {
-            cv = R.col[start[u] + base + lane];
-            if (HAS_CS) wq = R.colscale[cv];
-          }
-        }
-        const int m = (nn - base) < 64 ? (nn - base) : 64;
-        for (int k = 0; k < m; k += 2) {
-          const bool two = k + 1 < m;
-          const int c0 = __builtin_amdgcn_readlane(cv, k);
-          const int c1 = __builtin_amdgcn_readlane(cv, two ? k + 1 : k);
-          float w0 = 1.f, w1 = 1.f;
-          if (HAS_CS) {
-            w0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wq), k));
-            w1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wq), two ? k + 1 : k));
-          }
-          const char* b0 = src + static_cast<int64_t>(c0) * ldb;
-          const char* b1 = src + static_cast<int64_t>(c1) * ldb;
-          float4 v0[CH], v1[CH];
-#pragma unroll
-          for (int c = 0; c < CH; ++c) v0[c] = *reinterpret_cast<const float4*>(b0 + (loff + c * 1024u));
-          if (two) {
-#pragma unroll
-            for (int c = 0; c < CH; ++c) v1[c] = *reinterpret_cast<const float4*>(b1 + (loff + c * 1024u));
-          }
-#pragma unroll
-          for (int c = 0; c < CH; ++c) f4_fma(acc[c], w0, v0[c]);
-          if (two) {
-#pragma unroll
-            for (int c = 0; c < CH; ++c) f4_fma(acc[c], w1, v1[c]);
-          }
-        }
-      }
-      const float inv = __builtin_amdgcn_rcpf(static_cast<float>(nn > 1 ? nn : 1));
-      if (a.inv_cnt != nullptr && lane == 0) a.inv_cnt[static_cast<int64_t>(r0 + u) * a.n_rows + row] = inv;
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        if (SELF) f4_add(acc[c], selfv[SELF ? c : 0]);
-        if (mean) { acc[c].x *= inv; acc[c].y *= inv; acc[c].z *= inv; acc[c].w *= inv; }
-      }
-      if (SHARED) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) f4_add(tot[SHARED ? c : 0], acc[c]);
-      } else {
-        char* op = reinterpret_cast<char*>(a.out + static_cast<int64_t>(row) * a.ld_out + static_cast<int64_t>(r0 + u) * a.rel_stride);
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          float4 o = acc[c];
-          float4* q = reinterpret_cast<float4*>(op + (loff + c * 1024u));
-          if (accum) f4_add(o, *q);
-          *q = o;
-        }
-      }
-    }
-  }
-  if (SHARED) {
-    char* op = reinterpret_cast<char*>(a.out + static_cast<int64_t>(row) * a.ld_out);
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      float4 o = tot[SHARED ? c : 0];
-      float4* q = reinterpret_cast<float4*>(op + (loff + c * 1024u));
-      if (accum) f4_add(o, *q);
-      *q = o;
-    }
-  }
-}
-
-
-// ------------------------------------------------------------------------------------------
-// Fast path, straight-line index phase.  PMC on k_spmm_fast (profiles/r01_spmm_kernel_study.md, second part): at
-// full occupancy (8 waves / SIMD) a wave lives ~6 us, 55 % of it in s_waitcnt, and the launch takes two such
-// rounds — the kernel is bound by the LENGTH OF THE DEPENDENT-LOAD CHAIN of one row, not by bytes.  The chain in
-// k_spmm_fast: per relation {pointer from the kernel-argument table -> rowptr[row] -> rowptr[row+1]} one after the
-// other, then the column ids, then per relation {gather -> store}, with every later gather also waiting for the
-// previous relation's store (vmcnt counts loads and stores in issue order).  Here:
+// Fast path (H exactly 256 or 512, no per-edge weight, no ACCUM: host-side check; everything else takes k_spmm_s above, same
+// results up to the ulp of the v_rcp_f32 that stands for the division by the count here), straight-line index phase.  PMC on
+// the generic kernel (profiles/r01_spmm_kernel_study.md): ~1000 instructions per row, the aggregation was INSTRUCTION-ISSUE
+// bound (rows have ~1.6 neighbours per relation), not bandwidth bound.  PMC on this kernel's predecessor, which took the
+// relations four at a time with a segment's column ids in one VGPR (second part of that study; the kernel itself is gone, its
+// numbers are in the profiles): at full occupancy (8 waves / SIMD) a wave lives ~6 us, 55 % of it in s_waitcnt, and the launch
+// takes two such rounds — bound by the LENGTH OF THE DEPENDENT-LOAD CHAIN of one row, not by bytes.  That chain was: per
+// relation {pointer from the kernel-argument table -> rowptr[row] -> rowptr[row+1]} one after the other, then the column ids,
+// then per relation {gather -> store}, with every later gather also waiting for the previous relation's store (vmcnt counts
+// loads and stores in issue order).  Here:
 //   * the table is a structure of arrays, so the four rowptr / rowend / col / src pointers come with one scalar load
 //     each, and entries beyond n_rel repeat the last relation: no branch anywhere in the index phase;
 //   * a row's end comes from its own pointer: the relation's `rowend` array when the batch is trimmed (PyG
@@ -345,7 +192,8 @@ __global__ __launch_bounds__(256) void k_spmm_fast(RelTable t, SpmmArgs a) {
 // A row therefore costs rowptr -> col -> gather.  Loads are unconditional: lanes beyond the neighbour count repeat
 // the last neighbour (an L1 hit) or, for an empty segment, row 0, and what they fetch is dropped by a per-lane
 // select (not a multiply by zero: a non-finite value must not leak).  Neighbours beyond the second (rare) take the
-// two-at-a-time loop of k_spmm_fast.
+// two-at-a-time loop below the reduction: ids and scales by v_readlane from the segment's registers, or, for a row with
+// more than 64 neighbours in one relation, by scalar loads.
 // FILT adds the two per-edge predicates of the C-ABI (column < col_limit: the backward pass of a trimmed layer;
 // column != row: the onset pooling, models/analysis.py:581-584).  They are evaluated once per column-id vector and kept
 // as a 64-bit wave mask in SGPRs: a neighbour's "keep" bit is a scalar shift, the valid count one s_bcnt1.
@@ -372,9 +220,6 @@ __device__ __forceinline__ int to_vgpr(int s) {
   int v;
   asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(s));
   return v;
-}
-__device__ __forceinline__ float4 f4_keep(bool keep, const float4& v) {
-  return make_float4(keep ? v.x : 0.f, keep ? v.y : 0.f, keep ? v.z : 0.f, keep ? v.w : 0.f);
 }
 
 // root + (w * s + acc) with every step rounded (no fused multiply-add): k_spmm_self_grad's product and sum, then autograd's add
@@ -614,7 +459,7 @@ __global__ __launch_bounds__(256) void k_spmm_fast7(FastTable t, SpmmArgs a) {
       for (int c = 0; c < CH; ++c) {
         float4& o = v0[u][c];
         if (SELF && !root) f4_add(o, selfv[SELF ? c : 0]);
-        o.x *= inv; o.y *= inv; o.z *= inv; o.w *= inv;
+        f4_scale(o, inv);
       }
       if (SHARED) {
 #pragma unroll
@@ -646,14 +491,14 @@ __global__ __launch_bounds__(256) void k_spmm_fast7(FastTable t, SpmmArgs a) {
       sum += (v[c].x + v[c].y) + (v[c].z + v[c].w);
     }
     const float invS = 1.f / static_cast<float>(2 * a.H);
-    const float m = agnn::wave_sum_dpp(sum) * invS;
+    const float m = wave_sum_dpp(sum) * invS;
     float q = 0.f;
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
       const float dx = v[c].x - m, dy = v[c].y - m, dz = v[c].z - m, dw = v[c].w - m;
       q += fmaf(dx, dx, dy * dy) + fmaf(dz, dz, dw * dw);     // spelled out as k_na_fwd's expression is contracted: the same bits
     }
-    const float rs = 1.f / sqrtf(fmaf(agnn::wave_sum_dpp(q), invS, a.eps));
+    const float rs = 1.f / sqrtf(fmaf(wave_sum_dpp(q), invS, a.eps));
     if (lane == 0) { a.mean[row] = m; a.rstd[row] = rs; }
     char* yp = reinterpret_cast<char*>(a.y + static_cast<int64_t>(row) * a.ld_y);
 #pragma unroll
@@ -686,20 +531,12 @@ __global__ __launch_bounds__(256) void k_spmm_fast7(FastTable t, SpmmArgs a) {
   }
 }
 
-template <int CH>
-void launch_fast(hipStream_t stream, const RelTable& t, const SpmmArgs& a, bool has_cs, bool filt) {
-  const bool shared = a.rel_stride == 0, self = a.self != nullptr;
-  const bool v4 = (a.flags & AGNN_SPMM_FAST_V4) != 0 || (a.flags & AGNN_SPMM_ACCUM) != 0;
-  // Rows per wave: one.  More than one (consecutive rows sharing one index phase) measured SLOWER at the C2 shape, both
-  // with the rows' gathers in flight together (95 VGPRs -> 5 waves / SIMD: forward 17.1 us vs 15.5 us) and one row after
-  // the other on the same registers (16.5 us; backward 18.1 vs 15.5 us): vmcnt counts in issue order, so the second
-  // row's gathers cannot be consumed before the first row's stores are acknowledged, whereas a wave that ends after
-  // its stores hands its slot to a new wave at once (round 1, profiles/r01_spmm_kernel_study.md).
-  const dim3 grid(static_cast<unsigned>(((a.n_rows + 3) / 4 + 7) & ~7));   // multiple of 8: the XCD remap is a bijection
+// the structure-of-arrays table of n_rel relations; the tail repeats the last one, so the kernel's unconditional loads stay valid
+FastTable fast_table(const agnn_rel_t* rels, int n_rel) {
   FastTable f{};
-  f.n_rel = t.n_rel;
+  f.n_rel = n_rel;
   for (int r = 0; r < AGNN_MAX_SEG + 3; ++r) {
-    const agnn_rel_t& R = t.r[r < t.n_rel ? r : t.n_rel - 1];     // the tail repeats the last relation: loads stay valid
+    const agnn_rel_t& R = rels[r < n_rel ? r : n_rel - 1];
     f.rowptr[r] = R.rowptr;
     f.rowend[r] = R.rowend != nullptr ? R.rowend : R.rowptr + 1;   // untrimmed: row i ends where row i + 1 starts
     f.col[r] = R.col;
@@ -707,10 +544,22 @@ void launch_fast(hipStream_t stream, const RelTable& t, const SpmmArgs& a, bool 
     f.colscale[r] = R.colscale;
     f.ldb[r] = static_cast<uint32_t>(R.ld_src * 4);
   }
+  return f;
+}
+
+template <int CH>
+void launch_fast(hipStream_t stream, const RelTable& t, const SpmmArgs& a, bool has_cs, bool filt) {
+  const bool shared = a.rel_stride == 0, self = a.self != nullptr;
+  // Rows per wave: one.  More than one (consecutive rows sharing one index phase) measured SLOWER at the C2 shape, both
+  // with the rows' gathers in flight together (95 VGPRs -> 5 waves / SIMD: forward 17.1 us vs 15.5 us) and one row after
+  // the other on the same registers (16.5 us; backward 18.1 vs 15.5 us): vmcnt counts in issue order, so the second
+  // row's gathers cannot be consumed before the first row's stores are acknowledged, whereas a wave that ends after
+  // its stores hands its slot to a new wave at once (round 1, profiles/r01_spmm_kernel_study.md).
+  const dim3 grid(grid_for(a.n_rows));
+  const FastTable f = fast_table(t.r, t.n_rel);
 #define AGNN_FAST(CS, SH, SE)                                                                                     \
   do {                                                                                                            \
-    if (v4) hipLaunchKernelGGL((k_spmm_fast<CH, CS, SH, SE>), grid, dim3(256), 0, stream, t, a);                  \
-    else if (filt) hipLaunchKernelGGL((k_spmm_fast7<CH, CS, SH, SE, true>), grid, dim3(256), 0, stream, f, a);    \
+    if (filt) hipLaunchKernelGGL((k_spmm_fast7<CH, CS, SH, SE, true>), grid, dim3(256), 0, stream, f, a);         \
     else hipLaunchKernelGGL((k_spmm_fast7<CH, CS, SH, SE, false>), grid, dim3(256), 0, stream, f, a);             \
   } while (0)
   if (has_cs) {
@@ -724,8 +573,9 @@ void launch_fast(hipStream_t stream, const RelTable& t, const SpmmArgs& a, bool 
 }
 
 template <int CH>
-void launch_s(dim3 grid, hipStream_t stream, const RelTable& t, const SpmmArgs& a) {
+void launch_s(hipStream_t stream, const RelTable& t, const SpmmArgs& a) {
   const bool shared = a.rel_stride == 0, self = a.self != nullptr;
+  const dim3 grid(grid_for(a.n_rows));
   if (shared && self) hipLaunchKernelGGL((k_spmm_s<CH, true, true>), grid, dim3(256), 0, stream, t, a);
   else if (shared) hipLaunchKernelGGL((k_spmm_s<CH, true, false>), grid, dim3(256), 0, stream, t, a);
   else if (self) hipLaunchKernelGGL((k_spmm_s<CH, false, true>), grid, dim3(256), 0, stream, t, a);
@@ -757,11 +607,10 @@ __global__ __launch_bounds__(256) void k_spmm_self_grad(const float* __restrict_
 extern "C" int agnn_spmm_self_grad_f32(const float* dout, int64_t ld_dout, int64_t rel_stride, int32_t n_rel, const float* inv_cnt,
                                        int64_t ld_inv, int64_t n_rows, int32_t H, float* out, int64_t ld_out, int32_t accumulate,
                                        agnn_stream_t stream_) {
-  using namespace agnn;
   if (n_rel <= 0 || n_rows < 0 || H <= 0 || (H & 3)) return fail(AGNN_EINVAL, "spmm_self_grad: n_rel=%d n_rows=%lld H=%d (H must be a multiple of 4)", n_rel, (long long)n_rows, H);
   if (n_rows == 0) return AGNN_OK;
   if (!dout || !out) return fail(AGNN_EINVAL, "spmm_self_grad: null argument");
-  if (!aligned16(dout) || !aligned16(out) || (ld_dout & 3) || (ld_out & 3) || (rel_stride & 3) || ld_out < H || ld_dout < H)
+  if (!f4_rows(dout, ld_dout, H) || !f4_rows(out, ld_out, H) || (rel_stride & 3))
     return fail(AGNN_EALIGN, "spmm_self_grad: operands must be 16-byte aligned with leading dimensions >= H");
   if (inv_cnt && ld_inv < n_rows) return fail(AGNN_EINVAL, "spmm_self_grad: ld_inv=%lld < n_rows", (long long)ld_inv);
   const int64_t total = n_rows * (H / 4);
@@ -781,17 +630,16 @@ int spmm_entry(int n_rel, const agnn_rel_t* rels, int64_t n_rows, int32_t H, flo
 extern "C" int agnn_spmm_f32(int n_rel, const agnn_rel_t* rels, int64_t n_rows, int32_t H, float* out,
                              int64_t ld_out, int64_t rel_stride, const float* self, int64_t ld_self,
                              float* inv_cnt, int32_t col_limit, uint32_t flags, agnn_stream_t stream_) {
-  if (flags & AGNN_SPMM_ROOT) return agnn::fail(AGNN_EINVAL, "spmm: AGNN_SPMM_ROOT is agnn_spmm_root_f32's flag");
+  if (flags & AGNN_SPMM_ROOT) return fail(AGNN_EINVAL, "spmm: AGNN_SPMM_ROOT is agnn_spmm_root_f32's flag");
   return spmm_entry(n_rel, rels, n_rows, H, out, ld_out, rel_stride, self, ld_self, n_rows, inv_cnt, col_limit, flags, stream_);
 }
 
 extern "C" int agnn_spmm_root_f32(int n_rel, const agnn_rel_t* rels, int64_t n_rows, int32_t H, float* out, int64_t ld_out,
                                   int64_t rel_stride, const float* root, int64_t ld_root, int64_t root_rows, float* inv_cnt,
                                   int32_t col_limit, uint32_t flags, agnn_stream_t stream_) {
-  using namespace agnn;
   if (!root || root_rows < 0) return fail(AGNN_EINVAL, "spmm_root: null root operand or root_rows=%lld", (long long)root_rows);
   if (rel_stride != 0 && root_rows < n_rows) return fail(AGNN_EINVAL, "spmm_root: the root slot needs a row per output row (root_rows=%lld < n_rows=%lld)", (long long)root_rows, (long long)n_rows);
-  if (flags & (AGNN_SPMM_ACCUM | AGNN_SPMM_GENERIC | AGNN_SPMM_FAST_V4)) return fail(AGNN_EINVAL, "spmm_root: flags 0x%x not supported", flags);
+  if (flags & (AGNN_SPMM_ACCUM | AGNN_SPMM_GENERIC)) return fail(AGNN_EINVAL, "spmm_root: flags 0x%x not supported", flags);
   if (H != 256 && H != 512) return fail(AGNN_EINVAL, "spmm_root: H=%d (256 or 512: the widths the specialised kernel is built for)", H);
   if (rel_stride != 0 && ld_out < n_rel * rel_stride + H) return fail(AGNN_EINVAL, "spmm_root: ld_out=%lld has no room for the root slot", (long long)ld_out);
   for (int r = 0; rels && r < n_rel && r < AGNN_MAX_SEG; ++r)
@@ -804,47 +652,40 @@ namespace {
 int spmm_entry(int n_rel, const agnn_rel_t* rels, int64_t n_rows, int32_t H, float* out, int64_t ld_out, int64_t rel_stride,
                const float* self, int64_t ld_self, int64_t self_rows, float* inv_cnt, int32_t col_limit, uint32_t flags,
                agnn_stream_t stream_) {
-  using namespace agnn;
   if (n_rel <= 0 || n_rel > AGNN_MAX_SEG) return fail(AGNN_EINVAL, "spmm: n_rel=%d not in [1,%d]", n_rel, AGNN_MAX_SEG);
-  if (n_rows < 0 || n_rows >= (int64_t{1} << 31)) return fail(AGNN_EINVAL, "spmm: n_rows=%lld", (long long)n_rows);
-  if (H <= 0 || (H & 3) != 0 || H > 1024) return fail(AGNN_EINVAL, "spmm: H=%d must be a multiple of 4 in [4,1024]", H);
-  if (n_rows == 0) return AGNN_OK;
+  if (int rc = check_wave_rows("spmm", n_rows, H)) return rc > 0 ? AGNN_OK : rc;
   if (!rels || !out) return fail(AGNN_EINVAL, "spmm: null argument");
   if (!aligned16(out) || (ld_out & 3) || (rel_stride & 3) || ld_out < H) return fail(AGNN_EALIGN, "spmm: out/ld_out/rel_stride must be 16-byte aligned and ld_out >= H");
   if (rel_stride != 0 && rel_stride < H) return fail(AGNN_EINVAL, "spmm: rel_stride=%lld < H", (long long)rel_stride);
-  if (self && (!aligned16(self) || (ld_self & 3) || ld_self < H)) return fail(AGNN_EALIGN, "spmm: self misaligned");
+  if (self && !f4_rows(self, ld_self, H)) return fail(AGNN_EALIGN, "spmm: self misaligned");
   RelTable t{};
   t.n_rel = n_rel;
   for (int r = 0; r < n_rel; ++r) {
     if (!rels[r].rowptr) return fail(AGNN_EINVAL, "spmm: relation %d has null rowptr", r);
-    if (rels[r].src && (!aligned16(rels[r].src) || (rels[r].ld_src & 3) || rels[r].ld_src < H)) return fail(AGNN_EALIGN, "spmm: relation %d src misaligned or ld_src < H", r);
+    if (rels[r].src && !f4_rows(rels[r].src, rels[r].ld_src, H)) return fail(AGNN_EALIGN, "spmm: relation %d src misaligned or ld_src < H", r);
     t.r[r] = rels[r];
   }
   SpmmArgs a{static_cast<int32_t>(n_rows), H, out, ld_out, rel_stride, self, ld_self, inv_cnt, col_limit, flags, static_cast<int32_t>(self_rows)};
-  int64_t blocks = ((n_rows + 3) / 4 + 7) & ~int64_t{7};   // multiple of 8: the XCD remap is a bijection
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (!(flags & AGNN_SPMM_GENERIC) && (H == 256 || H == 512)) {
-    // fast path: everything except per-edge weights; trimmed rows (rowend) cost nothing extra, the per-edge predicates
-    // (SKIP_SELF, col_limit) select the FILT instantiation; the older v4 kernel (ACCUM, A/B timing) knows neither
+  if (!(flags & (AGNN_SPMM_GENERIC | AGNN_SPMM_ACCUM)) && (H == 256 || H == 512)) {
+    // fast path: everything except per-edge weights and ACCUM; trimmed rows (rowend) cost nothing extra, the per-edge
+    // predicates (SKIP_SELF, col_limit) select the FILT instantiation
     const bool filt = (flags & AGNN_SPMM_SKIP_SELF) != 0 || col_limit != INT32_MAX;
-    const bool v4 = (flags & (AGNN_SPMM_FAST_V4 | AGNN_SPMM_ACCUM)) != 0;
     bool plain = true, any_cs = false, all_cs = true;
     for (int r = 0; r < n_rel; ++r) {
       plain = plain && rels[r].ew == nullptr && rels[r].src != nullptr && rels[r].col != nullptr &&
-              rels[r].ld_src < (int64_t{1} << 30) && !(v4 && rels[r].rowend != nullptr);
+              rels[r].ld_src < (int64_t{1} << 30);
       any_cs = any_cs || rels[r].colscale != nullptr;
       all_cs = all_cs && rels[r].colscale != nullptr;
     }
-    if (plain && any_cs == all_cs && !(v4 && filt)) {
+    if (plain && any_cs == all_cs) {
       if (H == 256) launch_fast<1>(stream, t, a, all_cs, filt);
       else launch_fast<2>(stream, t, a, all_cs, filt);
       return check_launch("spmm(fast)");
     }
   }
   if (flags & AGNN_SPMM_ROOT) return fail(AGNN_EINVAL, "spmm_root: this launch is outside the specialised kernel (missing src / col, or mixed column scales)");
-  if (H <= 256) launch_s<1>(dim3(blocks), stream, t, a);
-  else if (H <= 512) launch_s<2>(dim3(blocks), stream, t, a);
-  else launch_s<4>(dim3(blocks), stream, t, a);
+  for_width(H, [&](auto ch) { launch_s<decltype(ch)::value>(stream, t, a); });
   return check_launch("spmm");
 }
 }  // namespace
@@ -854,7 +695,6 @@ int spmm_entry(int n_rel, const agnn_rel_t* rels, int64_t n_rows, int32_t H, flo
 // ------------------------------------------------------------------------------------------
 namespace {
 int join_check(const char* who, const agnn_rel_t* rel, int64_t n, int64_t pool_rows, int32_t H, int32_t col_limit) {
-  using namespace agnn;
   if (H != 256 && H != 512) return fail(AGNN_EINVAL, "%s: H=%d (256 or 512: the widths the specialised kernel is built for)", who, H);
   if (n < 0 || n >= (int64_t{1} << 31) || pool_rows < 1 || pool_rows > n || col_limit < 0) return fail(AGNN_EINVAL, "%s: n=%lld pool_rows=%lld (1 <= pool_rows <= n) col_limit=%d", who, (long long)n, (long long)pool_rows, col_limit);
   if (!rel || !rel->rowptr || !rel->col) return fail(AGNN_EINVAL, "%s: null index", who);
@@ -864,25 +704,13 @@ int join_check(const char* who, const agnn_rel_t* rel, int64_t n, int64_t pool_r
 
 template <int CH, bool HAS_CS, int EPI>
 void launch_join(hipStream_t stream, const agnn_rel_t& R, const SpmmArgs& a) {
-  const dim3 grid(static_cast<unsigned>(((a.n_rows + 3) / 4 + 7) & ~7));   // multiple of 8: the XCD remap is a bijection
-  FastTable f{};
-  f.n_rel = 1;
-  for (int r = 0; r < AGNN_MAX_SEG + 3; ++r) {
-    f.rowptr[r] = R.rowptr;
-    f.rowend[r] = R.rowend != nullptr ? R.rowend : R.rowptr + 1;
-    f.col[r] = R.col;
-    f.src[r] = R.src;
-    f.colscale[r] = R.colscale;
-    f.ldb[r] = static_cast<uint32_t>(R.ld_src * 4);
-  }
-  hipLaunchKernelGGL((k_spmm_fast7<CH, HAS_CS, true, true, true, EPI>), grid, dim3(256), 0, stream, f, a);
+  hipLaunchKernelGGL((k_spmm_fast7<CH, HAS_CS, true, true, true, EPI>), dim3(grid_for(a.n_rows)), dim3(256), 0, stream, fast_table(&R, 1), a);
 }
 }  // namespace
 
 extern "C" int agnn_pool_cat_norm_f32(const agnn_rel_t* rel, const float* x, int64_t ld_x, int64_t n, int64_t pool_rows, int32_t H,
                                       int32_t col_limit, const float* gamma, const float* beta, float eps, float* u, int64_t ld_u,
                                       float* y, int64_t ld_y, float* mean, float* rstd, float* inv_cnt, agnn_stream_t stream_) {
-  using namespace agnn;
   if (n == 0) return AGNN_OK;
   if (int rc = join_check("pool_cat_norm", rel, n, pool_rows, H, col_limit)) return rc;
   if (!x || !gamma || !beta || !u || !y || !mean || !rstd) return fail(AGNN_EINVAL, "pool_cat_norm: null argument");
@@ -920,7 +748,6 @@ extern "C" int agnn_pool_cat_norm_f32(const agnn_rel_t* rel, const float* x, int
 
 extern "C" int agnn_pool_cat_bwd_f32(const agnn_rel_t* rel_t, const float* du, int64_t ld_du, const float* inv_cnt, int64_t n,
                                      int64_t pool_rows, int32_t H, float* dx, int64_t ld_dx, agnn_stream_t stream_) {
-  using namespace agnn;
   if (n == 0) return AGNN_OK;
   if (int rc = join_check("pool_cat_bwd", rel_t, n, pool_rows, H, 0)) return rc;
   if (!du || !inv_cnt || !dx) return fail(AGNN_EINVAL, "pool_cat_bwd: null argument");

@@ -15,7 +15,7 @@ from analysisgnn_amd import ops  # noqa: E402
 from analysisgnn_amd.graph import HeteroIndex  # noqa: E402
 from analysisgnn_amd.synth import make_batch  # noqa: E402
 
-VARIANTS = {"generic": 1024, "fast_v4": 2048, "fast": 0}
+VARIANTS = {"generic": 1024, "fast": 0}
 REP = 10
 
 

@@ -86,7 +86,7 @@ def _spmm_case(n_dst, n_src, es, H, mean, shared, with_self, skip_self=False, co
     """ew: True (every relation) or one bool per relation — random per-edge weights in COO order, zeros and negative values
     among them, brought to CSR position order by ops._perm_weights for the kernel and by the oracle's own `perm` for the
     oracle.  accum: `out` is prefilled with known random values and AGNN_SPMM_ACCUM is set; expected = prefill + oracle.
-    variant: ops.SPMM_VARIANT for this launch (1024 = AGNN_SPMM_GENERIC, 2048 = AGNN_SPMM_FAST_V4)."""
+    variant: ops.SPMM_VARIANT for this launch (1024 = AGNN_SPMM_GENERIC)."""
     from analysisgnn_amd import _lib, ops
     dev = _dev()
     rng = np.random.default_rng(seed)
@@ -187,10 +187,6 @@ def test_spmm_heavy_row_and_empty_rows():
     # the same through the backward configuration of the fast path (column scales, relations summed into one slot)
     _spmm_case(40, 500, [3000, 70], 256, mean=False, shared=True, with_self=False, seed=4, colscale=True)
     _spmm_case(33, 500, [2500, 0, 9], 512, mean=True, shared=False, with_self=True, seed=5)
-    # the older fast kernel (AGNN_SPMM_FAST_V4, the A/B yardstick of scripts/spmm_ab.py): second and later 64-id batches, an odd tail
-    _spmm_case(40, 500, [3000], 256, mean=True, shared=False, with_self=False, seed=3, variant=2048)
-    _spmm_case(40, 500, [3000, 70], 256, mean=False, shared=True, with_self=False, seed=4, colscale=True, variant=2048)
-    _spmm_case(33, 500, [2500, 0, 9], 512, mean=True, shared=False, with_self=True, seed=5, variant=2048)
 
 
 def test_spmm_filters_and_trim():
@@ -212,20 +208,18 @@ def test_fast_and_generic_kernels_agree():
                 _spmm_case(300, 300, [1500, 2, 700, 0, 90], H, seed=H, **kw)
             finally:
                 ops.SPMM_VARIANT = 0
-            # the older fast kernel (AGNN_SPMM_FAST_V4): 5 relations = one full group of four and a partly filled one, an
-            # empty relation; then rows with more than 64 neighbours
-            _spmm_case(300, 300, [1500, 2, 700, 0, 90], H, seed=H, variant=2048, **kw)
-            _spmm_case(40, 300, [3000, 0, 100, 2500, 7], H, seed=H + 1, variant=2048, **kw)
+            # 5 relations = one full group of four and a partly filled one, an empty relation, and rows with more than 64
+            # neighbours in three of them
+            _spmm_case(40, 300, [3000, 0, 100, 2500, 7], H, seed=H + 1, **kw)
 
 
 @pytest.mark.parametrize("H", [256, 512])
-@pytest.mark.parametrize("variant", [0, 1024, 2048])
+@pytest.mark.parametrize("variant", [0, 1024])
 def test_fast_path_trimmed_and_filtered(H, variant):
     """What a training step of the reference launches (models/analysis.py:960-961 always passes the per-hop counts, so
     every layer is trimmed): row ends from `rowend` (forward), `rowend` + column limit + 1/deg column scales (backward),
     and the onset pooling's predicates (models/analysis.py:581-584) — through the fast kernel (k_spmm_fast7, FILT and
-    plain) and through the generic one, each against the C oracle.  AGNN_SPMM_FAST_V4 (2048) asks for the older fast
-    kernel, which knows neither a trim nor a filter: the dispatcher must fall back to the generic kernel and still match."""
+    plain) and through the generic one (AGNN_SPMM_GENERIC, 1024), each against the C oracle."""
     from analysisgnn_amd import ops
     ops.SPMM_VARIANT = variant
     try:
@@ -292,7 +286,7 @@ def test_spmm_edge_weights(H):
 
 
 @pytest.mark.parametrize("H", [256, 512])
-@pytest.mark.parametrize("variant", [0, 2048])
+@pytest.mark.parametrize("variant", [0])                       # the dispatcher's own choice
 def test_spmm_edge_weights_leave_the_fast_path(H, variant):
     """At the widths of the specialised kernels, which read no `ew`: every relation weighted, and only one of three — the
     whole launch must go through the generic kernel, the unweighted relations included."""
@@ -312,10 +306,11 @@ def test_spmm_accumulate_generic_kernel(H):
 
 
 @pytest.mark.parametrize("H", [256, 512])
-def test_spmm_accumulate_reaches_the_older_fast_kernel(H):
-    """AGNN_SPMM_ACCUM at H = 256 / 512 selects k_spmm_fast: shared and per-relation slots (5 relations, one empty, a row of
-    more than 64 neighbours), with the self term, with column scales; under SKIP_SELF, which that kernel does not know, the
-    launch must fall back to the generic kernel and still accumulate."""
+def test_spmm_accumulate_at_the_fast_widths(H):
+    """AGNN_SPMM_ACCUM at H = 256 / 512, the widths of the specialised kernel, which does not accumulate: the launch goes
+    through the generic kernel, as at every other width, and adds exactly once per slot — shared and per-relation slots
+    (5 relations, one empty, a row of more than 64 neighbours), with the self term, with column scales, under SKIP_SELF
+    and under a trim."""
     _spmm_case(300, 300, [1500, 2, 700, 0, 90], H, mean=True, shared=False, with_self=False, accum=True, seed=H)
     _spmm_case(300, 300, [1500, 2, 700, 0, 90], H, mean=True, shared=False, with_self=True, accum=True, seed=H + 1)
     _spmm_case(300, 300, [1500, 2, 700, 0, 90], H, mean=True, shared=True, with_self=True, accum=True, seed=H + 2)
