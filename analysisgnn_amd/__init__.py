@@ -11,6 +11,8 @@ _PRETRAIN = ("PreEncoder", "pretrain_objective", "PretrainMetrics", "LinkPlan", 
 _EDGE_LOSS = ("EdgeDecoder", "EdgePlan", "edge_plan", "edge_consistency_loss")
 _SCORE_GRAPH = ("DeviceScoreGraph", "build_score_graph", "sort_notes")
 _DESCRIPTORS = ("note_features", "VOICE_FEATURES", "CADENCE_FEATURES")
+_PITCH_SPELLING = ("PKSpell", "HierarchicalHeteroGraphSage", "PitchSpellingGNN", "PitchSpellingNeighborGNN", "GraphNorm", "GraphSegments",
+                   "graph_norm", "graph_segments", "clear_segment_cache", "pitch_spelling_loss")
 
 
 def __getattr__(name):
@@ -29,4 +31,7 @@ def __getattr__(name):
     if name in _DESCRIPTORS:
         from . import descriptors
         return getattr(descriptors, name)
+    if name in _PITCH_SPELLING:
+        from . import pitch_spelling
+        return getattr(pitch_spelling, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

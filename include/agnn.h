@@ -43,6 +43,8 @@
  *   agnn_colnorm_*        `activation -> BatchNorm1d -> Dropout` over the row axis (ref: models/chord.py:569-570, core/mlp.py:27-35)
  *   agnn_onset_pool_*     `OnsetEdgePoolingVersion2`: scatter-mean over onset neighbours and self, selected rows only
  *                         (ref: models/chord.py:284-287)
+ *   agnn_graphnorm_*      PyG `GraphNorm`: per-graph, per-column normalisation with a learnable mean scale (ref:
+ *                         models/pitch_spelling.py:158, :222)
  *
  * Conventions (all entry points)
  *   - plain pointers and sizes only; every `const T*`/`T*` marked (device) is device memory owned
@@ -1444,6 +1446,52 @@ int agnn_onset_pool_fwd_f32(const float* a, int64_t ld_a, int64_t n, int32_t H, 
 int agnn_onset_pool_bwd_f32(const float* g, int64_t ld_g, int64_t n_sel, int32_t H, int64_t n, const int32_t* d_rowptr,
                             const int32_t* s_rowptr, const int32_t* s_col, const int32_t* sel_rowptr, const int32_t* sel_k,
                             float* da, int64_t ld_da, agnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GraphNorm (csrc/graphnorm.hip): PyG `GraphNorm(C, eps)` over the rows of x [n, C] fp32 (row stride ld_x), per graph g and per
+ * column, as the reference's PitchSpellingGNN uses it (models/pitch_spelling.py:158, :222).  With I_g the rows of graph g:
+ *   m = mean_{I_g} x,  o = x - mean_scale * m,  v = mean_{I_g} o^2 (not the centred variance when mean_scale != 1),
+ *   y = weight * o / sqrt(v + eps) + bias.          Training and evaluation are the same function; no running statistics.
+ * The rows of graph g are rows[seg_ptr[g] .. seg_ptr[g + 1]) (int32; what agnn_csr_build returns for row = batch, col =
+ * arange(n), n_rows = G), so a sorted and an unsorted `batch` take the one path.  A graph may be empty (its stats are written as
+ * zeros, no row is touched) or have one row (with mean_scale = 1: y = bias).  seg_ptr is read through a clamp to [0, n] and a
+ * row index outside [0, n) is skipped, so an inconsistent index cannot make a kernel leave its operands.
+ *   agnn_graphnorm_slabs  writes the slab table of a batch from seg_ptr, once per batch: a slab is at most AGNN_GN_SLAB
+ *                  consecutive positions of ONE graph; the host knows only the bound ceil(n / AGNN_GN_SLAB) + G on their
+ *                  number, every grid is that bound and surplus workgroups exit.  table (caller-owned, int32,
+ *                  agnn_graphnorm_table_bytes(n, G)): the first slab of every graph [G + 1, padded to 4], then (graph, first
+ *                  position, count, 0) per slab.
+ *   forward        (a) per slab and column (count, mean, M2) of x - K, K = x[first row of the slab] (E[x^2] - mean^2 is never
+ *                  formed); (b) per graph the slabs' triples joined pairwise in slab order (AGNN_GN_JOIN_LANES lanes take slabs
+ *                  l, l + 16, ..., then lane order; Chan et al.), v = M2 / n + ((1 - mean_scale) m)^2, stats; (c) y.
+ *   backward       with ohat = o * rstd: do = weight * rstd * (g - ohat * mean_g(g * ohat)), dx = do - mean_scale * mean_g(do),
+ *                  dweight = sum g * ohat, dbias = sum g, dmean_scale = -sum_g n_g m_g mean_g(do).  (a) per slab the sums of
+ *                  g * ohat, g and o; (b) per graph their join in the same order; (c) dx, and the three parameter gradients as
+ *                  the sum of the graphs' terms in a fixed order (lanes take graphs l, l + 16, ..., then lane order).
+ * stats [G, 3, C] (caller-owned, written by forward, read by backward): the shift mean_scale * m as a sum of two floats (hi, lo)
+ * and rstd; y = ((x - hi) - lo) * rstd * weight + bias, which keeps a column with |mean| >> std exact.  m is NOT stored and NOT
+ * divided out of hi + lo (mean_scale may be 0): backward recomputes it as (hi + lo) + mean_g(o) from its third slab sum.
+ * The joins carry the row counts as floats: exact up to 2^24 rows in ONE graph, beyond that the join weights are rounded (relative
+ * 6e-8; n_g itself stays an integer in every division).
+ * No float atomics: two runs give the same bits.  C % 4 == 0, C >= 4, n < 2^31 (AGNN_EINVAL); x, y, dy, dx, the [C] vectors,
+ * stats, table and workspace 16-byte aligned, seg_ptr and rows 4-byte aligned, leading dimensions % 4 == 0 (AGNN_EALIGN);
+ * workspace >= agnn_graphnorm_workspace_bytes(n, G, C), table >= agnn_graphnorm_table_bytes(n, G) (AGNN_ENOMEM).  n == 0:
+ * AGNN_OK, no pointer is looked at; n > 0 with G == 0: AGNN_EINVAL.  Stream-ordered, no host read.
+ * ------------------------------------------------------------------------------------------ */
+#define AGNN_GN_SLAB   128
+#define AGNN_GN_JOIN_LANES 16
+size_t agnn_graphnorm_table_bytes(int64_t n, int64_t G);
+size_t agnn_graphnorm_workspace_bytes(int64_t n, int64_t G, int32_t C);
+int agnn_graphnorm_slabs(const int32_t* seg_ptr, int64_t n, int64_t G, int32_t* table, size_t table_bytes, agnn_stream_t stream);
+int agnn_graphnorm_fwd_f32(const float* x, int64_t ld_x, int64_t n, int64_t G, int32_t C, const int32_t* seg_ptr,
+                           const int32_t* rows, const int32_t* table, size_t table_bytes, const float* weight, const float* bias,
+                           const float* mean_scale, float eps, float* y, int64_t ld_y, float* stats, void* workspace,
+                           size_t workspace_bytes, agnn_stream_t stream);
+int agnn_graphnorm_bwd_f32(const float* x, int64_t ld_x, int64_t n, int64_t G, int32_t C, const int32_t* seg_ptr,
+                           const int32_t* rows, const int32_t* table, size_t table_bytes, const float* weight,
+                           const float* mean_scale, const float* stats, const float* dy, int64_t ld_dy, float* dx, int64_t ld_dx,
+                           float* dweight, float* dbias, float* dmean_scale, void* workspace, size_t workspace_bytes,
+                           agnn_stream_t stream);
 
 #ifdef __cplusplus
 }
