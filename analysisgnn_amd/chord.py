@@ -9,6 +9,7 @@ Two schedules differ from the reference's:
     heads' first layers are ONE stacked GEMM [N, T * hidden] and ONE such block, since batch statistics are per column;
   * onset pooling computes only the selected rows and pools BEFORE `trans` (`onset_pool`, csrc/onsetpool.hip): the weights of a
     mean sum to one, so trans(mean) == mean(trans), and the Linear runs on K rows instead of N.
+Also here: `PostProcessingMLTModel` (models/chord.py:751-783), whose LSTM runs the persistent kernels of lstm_seq.py.
 Not here: `idx=None` pooling (`__merge_edges__` returns a mask where chord.py:568 needs an index), unequal `lengths` (the
 reference then returns padded rows), and the classes DESIGN.md §19 lists as out of scope."""
 from __future__ import annotations
@@ -502,3 +503,57 @@ class MetricalChordPredictionModel(nn.Module):
         if not isinstance(self.classifier, MultiTaskMLP):
             raise AgnnError("forward_fused: the NADE chain has no side-by-side logits; use forward")
         return self.classifier.forward_fused(self.encode(x, edge_index, edge_type, onset_edges, onset_idx, lengths, **kwargs))
+
+
+class PostProcessingMLTModel(nn.Module):
+    """models/chord.py:751-783: a bidirectional LSTM over the per-task soft-maxes of a prediction model's outputs, `fc`, and one
+    Linear head per task.  `forward(x: {task: logits [T, C_t] or [B, T, C_t]})` -> {task: logits}.  The LSTM runs the persistent
+    kernels (lstm_seq.py) at n_hidden 64 or 128, the library RNN on the GPU otherwise.  The stages, and what each runs on:
+      1. the per-task soft-maxes side by side: T `F.softmax` calls and ONE `torch.cat` (the library has no kernel that writes a
+         soft-max into a column block of a wider matrix);
+      2. a 2-D input becomes one sequence [1, T, sum C];
+      3. `lstm_forward`;
+      4. activation(fc(h.squeeze())) — the reference's `squeeze()`, which also drops a batch of one;
+      5. `F.normalize`, then dropout on the library's random stream (pitch_spelling._drop);
+      6. the heads as ONE product on their stacked weights [sum C, n_hidden], at every width: they all read the same rows, and
+         `heads.grouped_projection` gives each group its own column window of the input, so it would need h repeated per task.
+    Not here: the Lightning module `PostChordPrediction`."""
+
+    def __init__(self, tasks, n_hidden, n_layers, activation=F.relu, dropout=0.0):
+        super().__init__()
+        self.tasks = tasks
+        self.n_hidden = n_hidden
+        self.n_layers = n_layers
+        logits_dim = sum(self.tasks.values())
+        self.lstm = nn.LSTM(logits_dim, n_hidden, n_layers, batch_first=True, bidirectional=True, dropout=dropout)
+        self.fc = nn.Linear(n_hidden * 2, n_hidden)
+        self.clf = nn.ModuleDict({task: nn.Linear(n_hidden, n_classes) for task, n_classes in self.tasks.items()})
+        self.dropout = nn.Dropout(dropout)
+        self.activation = activation
+
+    def forward(self, x):
+        from .lstm_seq import lstm_forward
+        from .pitch_spelling import _drop
+        tasks = list(self.tasks.keys())
+        _lib.require_gpu(*[x[t] for t in tasks])
+        if self.training and self.dropout.p > 0:
+            fused.advance_rng(x[tasks[0]].device)
+        h = torch.cat([F.softmax(x[t], dim=-1) for t in tasks], dim=-1)
+        if h.dim() == 2:
+            h = h.unsqueeze(0)
+        h = lstm_forward(self.lstm, h, self.training).squeeze()
+        lead = tuple(h.shape[:-1])
+        h = self.activation(linear(h.reshape(-1, h.shape[-1]), self.fc.weight, self.fc.bias))
+        h = _drop(F.normalize(h, p=2, dim=-1), self.dropout.p, self.training)
+        offs = [0]
+        for t in tasks:
+            offs.append(offs[-1] + self.clf[t].out_features)
+        logits = linear(h, _cat_params([self.clf[t].weight for t in tasks]), _cat_params([self.clf[t].bias for t in tasks]))
+        logits = logits.view(lead + (offs[-1],))
+        return {t: logits[..., offs[i]:offs[i + 1]] for i, t in enumerate(tasks)}
+
+    def predict(self, x):
+        out = self.forward({k: v for k, v in x.items() if k in self.tasks.keys()})
+        out["onset"] = x["onset"]
+        out["s_measure"] = x["s_measure"]
+        return out

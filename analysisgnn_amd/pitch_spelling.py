@@ -28,6 +28,7 @@ from .graph import SegSpec, build_csr, hetero_index
 from .gru import gru_forward
 from .heads import multitask_cross_entropy
 from .linear import Linear, linear, linear2
+from .lstm_seq import lstm_forward
 
 
 # ---- the per-batch index of GraphNorm ------------------------------------------------------------------------------------------
@@ -190,9 +191,11 @@ def _unpad(y: torch.Tensor, lens: Sequence[int]) -> torch.Tensor:
 
 
 def _rnn(rnn: nn.Module, x: torch.Tensor, training: bool) -> torch.Tensor:
-    """The persistent GRU kernels where they are built (bidirectional, 64 or 128 per direction), the library RNN on the GPU
-    otherwise (every LSTM, unidirectional cells, other widths)."""
-    return gru_forward(rnn, x, training) if isinstance(rnn, nn.GRU) else rnn(x)[0]
+    """The persistent GRU / LSTM kernels where they are built (bidirectional, 64 or 128 per direction), the library RNN on the GPU
+    otherwise (unidirectional cells, other widths)."""
+    if isinstance(rnn, nn.GRU):
+        return gru_forward(rnn, x, training)
+    return lstm_forward(rnn, x, training) if isinstance(rnn, nn.LSTM) else rnn(x)[0]
 
 
 def _drop(x: torch.Tensor, p: float, training: bool) -> torch.Tensor:
@@ -204,8 +207,8 @@ def _drop(x: torch.Tensor, p: float, training: bool) -> torch.Tensor:
 
 class PKSpell(nn.Module):
     """models/pitch_spelling.py:50-151: two stacked bidirectional RNNs on padded sentences, dropout, two top layers.
-    `forward(sentences [sum len, in_feats], sentences_len)` -> padded ([B, T, out_feats], [B, T, 15]).  `cell_type="GRU"` with
-    n_hidden // 2 of 64 or 128 runs the persistent GRU kernels; `cell_type="LSTM"`, `bidirectional=False` and every other width
+    `forward(sentences [sum len, in_feats], sentences_len)` -> padded ([B, T, out_feats], [B, T, 15]).  Either `cell_type` with
+    n_hidden // 2 of 64 or 128 runs its persistent kernels (gru.py, lstm_seq.py); `bidirectional=False` and every other width
     run the library RNN on the GPU.  Two defects of the reference have working equivalents here: `predict`
     returns the first l entries of row i (the reference indexes `[:l, i]` on a batch-first tensor), and `loss_computation` uses
     `out_feats`, 15 and the constructor's `ignore_index` values (the reference reads attributes that do not exist)."""

@@ -15,6 +15,7 @@
  *                         models/analysis.py:580-586) and PyG `SAGEConv` mean aggregation under
  *                         `HeteroConv` (ref: models/cadence.py:147-159,174)
  *   agnn_gru_fwd/bwd_f32  `torch.nn.GRU` of the hybrid sequence branch (ref: models/cadence.py:249-285)
+ *   agnn_lstm_seq_*       `torch.nn.LSTM` over long sequences (ref: models/pitch_spelling.py:50-151; models/chord.py:751-783)
  *   agnn_gated_*          `ResGatedGraphConv` edge gate + scatter (ref: core/gnn.py:246-257)
  *   agnn_absdiff_*        `RelEdgeConv` per-row sums of h_j and |h_i - h_j| (ref: core/gnn.py:99-105)
  *   agnn_norm_act_*       LayerNorm / ReLU / Dropout chains between the projections (ref: models/analysis.py:429-443)
@@ -242,6 +243,30 @@ int agnn_gru_bwd_f32(const float* dy, const float* y, const float* saved, const 
 /* hp [B, T, 2, hidden]: the previous hidden state of each direction (forward: y[b, t-1, :hidden], reverse:
  * y[b, t+1, hidden:], zero at the sequence ends) — the operand of the W_hh weight-gradient GEMMs, in one launch. */
 int agnn_gru_hprev_f32(const float* y, int64_t B, int64_t T, int32_t hidden, float* hp, agnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Persistent bidirectional LSTM layer over long sequences (csrc/lstmseq.hip) = one layer of
+ * `torch.nn.LSTM(batch_first=True, bidirectional=True)`, zero initial state, gate order i, f, g, o
+ * (ref: models/pitch_spelling.py:50-151 with cell_type="LSTM"; models/chord.py:751-783).
+ * hidden (per direction) is 64 or 128.  B >= 1 and T >= 1: empty work is the caller's to skip.
+ *   gi    [B, T, 2, 4*hidden]   x W_ih^T + b_ih for both directions (computed by the caller)
+ *   w_hh  [2, 4*hidden, hidden], b_hh [2, 4*hidden]
+ *   y     [B, T, 2*hidden]      forward | reverse halves, as nn.LSTM(batch_first) returns
+ *   saved [B, T, 2, 5, hidden]  i, f, g, o after their non-linearities, and c_t  (kept for the backward pass)
+ * Backward: given dy emits ONE dg [B, T, 2, 4*hidden], the gradient of the pre-activations: an LSTM adds its input-side and
+ * hidden-side terms before the non-linearity, so dg is the gradient w.r.t. gi and w.r.t. W_hh h + b_hh alike (db_ih == db_hh).
+ * hprev (optional) [B, T, 2, hidden]: h_{t-1} of each direction (zero at the chain's first step), copied from y by the walk —
+ * the right operand of the W_hh weight-gradient product; y may be NULL without it.
+ * Inter-layer dropout of `nn.LSTM(dropout=p)` rides along as in the GRU pair: drop_scale [B, T, 2*hidden] holds 0 or
+ * 1 / (1 - p) per element; forward additionally writes y_drop = y * drop_scale (the next layer's input), backward takes
+ * dy = d(y_drop) and applies the same factor.  Both NULL: no dropout.
+ * ------------------------------------------------------------------------------------------ */
+int agnn_lstm_seq_fwd_f32(const float* gi, const float* w_hh, const float* b_hh, int64_t B, int64_t T,
+                          int32_t hidden, float* y, float* saved, const float* drop_scale, float* y_drop,
+                          agnn_stream_t stream);
+int agnn_lstm_seq_bwd_f32(const float* dy, const float* y, const float* saved, const float* w_hh,
+                          int64_t B, int64_t T, int32_t hidden, float* dg, const float* drop_scale, float* hprev,
+                          agnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * HGT edge-softmax attention = message / softmax / aggregate of PyG `HGTConv`, reached through
