@@ -57,6 +57,22 @@ def assert_close_rel(a, b, tol, what="", floor=1e-7):
     assert err <= tol * scale + floor, f"{what}: max abs err {err:.3e} > {tol:.1e} * max|ref| {scale:.3g}"
 
 
+class Guarded:
+    """A [rows, cols] destination (leading dimension `ld`) inside a NaN-filled buffer: `guard` floats in front of it and behind
+    it, and whatever `ld` leaves between the rows."""
+
+    def __init__(self, rows, cols, ld=None, guard=8, device="cuda:0"):
+        self.rows, self.cols, self.ld, self.guard = rows, cols, ld or cols, guard
+        self.buf = torch.full((2 * guard + rows * self.ld,), float("nan"), dtype=torch.float32, device=device)
+        self.view = self.buf[guard:guard + rows * self.ld].view(rows, self.ld)[:, :cols]
+
+    def check(self, what):
+        inside = torch.zeros_like(self.buf, dtype=torch.bool)
+        inside[self.guard:self.guard + self.rows * self.ld].view(self.rows, self.ld)[:, :self.cols] = True
+        assert not torch.isnan(self.buf[inside]).any(), f"{what}: an element inside was left unwritten"
+        assert torch.isnan(self.buf[~inside]).all(), f"{what}: written outside the destination"
+
+
 class _DenseGrad(torch.autograd.Function):
     """Identity whose backward hands on a dense, freshly allocated copy of the gradient."""
 

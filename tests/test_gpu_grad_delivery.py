@@ -9,6 +9,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from helpers import Guarded as _Guarded  # noqa: E402        (the NaN-guarded destination, shared with test_gpu_dense_products.py)
+
 DEV = torch.device("cuda", 0)
 NAN = float("nan")
 AGNN_OK, AGNN_EINVAL, AGNN_EALIGN = 0, -22, -14        # include/agnn.h
@@ -16,22 +18,6 @@ AGNN_OK, AGNN_EINVAL, AGNN_EALIGN = 0, -22, -14        # include/agnn.h
 
 def _bits(t):
     return t.contiguous().view(torch.int32)
-
-
-class _Guarded:
-    """A [rows, cols] destination (leading dimension `ld`) inside a NaN-filled buffer: `guard` floats in front of it and behind
-    it, and whatever `ld` leaves between the rows."""
-
-    def __init__(self, rows, cols, ld=None, guard=8):
-        self.rows, self.cols, self.ld, self.guard = rows, cols, ld or cols, guard
-        self.buf = torch.full((2 * guard + rows * self.ld,), NAN, dtype=torch.float32, device=DEV)
-        self.view = self.buf[guard:guard + rows * self.ld].view(rows, self.ld)[:, :cols]
-
-    def check(self, what):
-        inside = torch.zeros_like(self.buf, dtype=torch.bool)
-        inside[self.guard:self.guard + self.rows * self.ld].view(self.rows, self.ld)[:, :self.cols] = True
-        assert not torch.isnan(self.buf[inside]).any(), f"{what}: an element inside was left unwritten"
-        assert torch.isnan(self.buf[~inside]).all(), f"{what}: written outside the destination"
 
 
 def _products():
