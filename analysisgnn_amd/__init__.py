@@ -14,6 +14,10 @@ _DESCRIPTORS = ("note_features", "VOICE_FEATURES", "CADENCE_FEATURES")
 _PITCH_SPELLING = ("PKSpell", "HierarchicalHeteroGraphSage", "PitchSpellingGNN", "PitchSpellingNeighborGNN", "GraphNorm", "GraphSegments",
                    "graph_norm", "graph_segments", "clear_segment_cache", "pitch_spelling_loss")
 
+# (cadence.HierarchicalHeteroGraphSage, a different class from the pitch-spelling one, is reached through its module)
+_CADENCE = ("GNN", "SMOTE", "cad_clf", "run_cad_clf", "balanced_cross_entropy", "cadence_training_loss", "cadence_validation_loss",
+            "cadence_metrics")
+
 
 def __getattr__(name):
     """The public names of the pretraining stage (analysisgnn_amd/pretrain.py), of the edge-consistency term
@@ -34,4 +38,7 @@ def __getattr__(name):
     if name in _PITCH_SPELLING:
         from . import pitch_spelling
         return getattr(pitch_spelling, name)
+    if name in _CADENCE:
+        from . import cadence
+        return getattr(cadence, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

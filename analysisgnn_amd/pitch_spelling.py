@@ -284,7 +284,8 @@ class HierarchicalHeteroGraphSage(nn.Module):
             self.convs.append(HeteroConv(edge_types, input_channels if i == 0 else hidden_channels, hidden_channels, "sum"))
         self.lin = nn.Linear(hidden_channels, out_channels)
 
-    def forward(self, x_dict, edge_index_dict, num_sampled_edges_dict=None, num_sampled_nodes_dict=None):
+    def _run(self, x_dict, edge_index_dict, num_sampled_edges_dict, num_sampled_nodes_dict):
+        """(lin(x_note), the COO prefixes the last layer keeps: what its trim_to_layer leaves of every edge list)."""
         _lib.require_gpu(*x_dict.values())
         plan = TrimPlan(self.num_layers, x_dict, edge_index_dict, num_sampled_nodes_dict, num_sampled_edges_dict)
         index = hetero_index(edge_index_dict, {k: int(v.shape[0]) for k, v in x_dict.items()})
@@ -292,7 +293,10 @@ class HierarchicalHeteroGraphSage(nn.Module):
         for i, conv in enumerate(self.convs):
             x_dict = conv(dict(x_dict), edge_index_dict, index, plan.n_keep[i], plan.e_keep[i])
             x_dict = {k: v.relu() for k, v in x_dict.items()}
-        return linear(x_dict["note"], self.lin.weight, self.lin.bias)
+        return linear(x_dict["note"], self.lin.weight, self.lin.bias), plan.e_keep[-1]
+
+    def forward(self, x_dict, edge_index_dict, num_sampled_edges_dict=None, num_sampled_nodes_dict=None):
+        return self._run(x_dict, edge_index_dict, num_sampled_edges_dict, num_sampled_nodes_dict)[0]
 
 
 def _heads(enc: int, pc: int, ks: int, dropout: float):

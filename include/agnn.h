@@ -216,6 +216,30 @@ int agnn_pool_cat_norm_f32(const agnn_rel_t* rel /* (host) */, const float* x, i
 int agnn_pool_cat_bwd_f32(const agnn_rel_t* rel_t /* (host) */, const float* du, int64_t ld_du, const float* inv_cnt, int64_t n,
                           int64_t pool_rows, int32_t H, float* dx, int64_t ld_dx, agnn_stream_t stream);
 
+/* Class-balanced cross entropy, the loss of the cadence models' validation steps (ref: models/cadence.py:425-434 and :535-544,
+ * `weight = 1 / (bincount(y) + 1e-6); F.cross_entropy(logits, y, weight=weight)`), csrc/balce.hip:
+ *     count_c = #{r : y_r == c},      w_c = 1 / (count_c + eps_w)
+ *     loss    = sum_r w_{y_r} (logsumexp(z_r) - z_r[y_r]) / sum_r w_{y_r}
+ *     dlogits[r, c] = w_{y_r} (softmax(z_r)[c] - [c == y_r]) / sum_r w_{y_r}        (optional, may be NULL)
+ * logits [n_rows, n_classes] with leading dimension ld (any alignment: rows are read float by float); labels int64 [n_rows]; a
+ * row whose label equals ignore_index is left out of the counts, both sums and gets a zero row of dlogits.  eps_w > 0 (the
+ * reference's 1e-6).  Outputs: class_count int64 [n_classes] and weight float [n_classes] (either may be NULL), loss (device
+ * scalar), dlogits [n_rows, >= n_classes] with leading dimension ld_d.  Three launches: a count pass, a row pass, a fixed-order
+ * sum of one partial per 256 rows.  A thread owns a row in the row pass (strided reads, a serial loop over the classes): the kernel is
+ * meant for the few classes of a cadence head, not for a wide one.  No float atomics: two runs give the same bits.
+ * If no row is valid the loss is 0 and dlogits is 0 — this library's rule for an empty task (agnn_train_loss_f32); torch
+ * returns NaN there.  A label outside [0, n_classes) that is not ignore_index contributes nothing, gets a zero row of dlogits
+ * and adds 1 to *status (device int32, may be NULL; torch: device assert).  The reference only evaluates this loss; the gradient
+ * is one more store in the row pass and makes the function usable as a training loss.
+ * `workspace`: agnn_balanced_ce_workspace_bytes(n_rows) bytes, 4-byte aligned, need not be cleared.
+ * AGNN_EINVAL: n_classes outside [1, AGNN_BCE_MAX_CLASSES], n_rows < 0, eps_w <= 0, loss or workspace NULL, logits or labels
+ * NULL with n_rows > 0, ld or ld_d < n_classes; AGNN_ENOMEM: workspace too small.  n_rows == 0 writes loss = 0. */
+#define AGNN_BCE_MAX_CLASSES 256
+size_t agnn_balanced_ce_workspace_bytes(int64_t n_rows);
+int agnn_balanced_ce_f32(const float* logits, int64_t ld, int64_t n_rows, int32_t n_classes, const int64_t* labels,
+                         int64_t ignore_index, float eps_w, int64_t* class_count, float* weight, float* loss, float* dlogits,
+                         int64_t ld_d, int32_t* status, void* workspace, size_t workspace_bytes, agnn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Persistent bidirectional GRU layer (one launch for all T steps), replacing `torch.nn.GRU` in the
  * hybrid branch (ref: models/cadence.py:249-285, models/analysis.py:527-537).  hidden must be 128
