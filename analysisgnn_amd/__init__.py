@@ -15,8 +15,8 @@ _PITCH_SPELLING = ("PKSpell", "HierarchicalHeteroGraphSage", "PitchSpellingGNN",
                    "graph_norm", "graph_segments", "clear_segment_cache", "pitch_spelling_loss")
 
 # (cadence.HierarchicalHeteroGraphSage, a different class from the pitch-spelling one, is reached through its module)
-_CADENCE = ("GNN", "SMOTE", "cad_clf", "run_cad_clf", "balanced_cross_entropy", "cadence_training_loss", "cadence_validation_loss",
-            "cadence_metrics")
+_CADENCE = ("GNN", "SMOTE", "CadenceGNNNeighbor", "CadenceGNNPytorch", "JoinNorm", "JoinIndex", "join_index", "pool_norm", "cad_clf",
+            "run_cad_clf", "balanced_cross_entropy", "cadence_training_loss", "cadence_validation_loss", "cadence_metrics")
 
 
 def __getattr__(name):

@@ -1,14 +1,14 @@
-"""Parts of the reference's cadence family (models/cadence.py) on the HIP kernels: the homogeneous `GNN`, the cadence
-`HierarchicalHeteroGraphSage` (which also returns the trimmed `edge_index_dict`), the classifier head both cadence models share,
-the class-balanced cross entropy of the validation steps (csrc/balce.hip) and the Lightning steps restated as functions:
-`cadence_training_loss`, `cadence_validation_loss`, `cadence_metrics`.  Same class names, constructor arguments and parameter names
-as the reference, so its `state_dict`s load by name.  `SMOTE` is smote.SMOTE, re-exported.  Inputs live on a HIP device; there is
-no CPU path.
+"""The reference's cadence family (models/cadence.py) on the HIP kernels: `CadenceGNNNeighbor` and `CadenceGNNPytorch`, the join
+`LayerNorm(scatter_mean(x[src], dst, out=x.clone()))` between their encoder and `pool_mlp` in one launch each way (`pool_norm`,
+csrc/pooljoin.hip), the homogeneous `GNN`, the cadence `HierarchicalHeteroGraphSage` (which also returns the trimmed
+`edge_index_dict`), the classifier head both models share, the class-balanced cross entropy of the validation steps
+(csrc/balce.hip) and the Lightning steps restated as functions: `cadence_training_loss`, `cadence_validation_loss`,
+`cadence_metrics`.  Same class names, constructor arguments and parameter names as the reference, so its `state_dict`s load by name
+with `strict=True`.  `SMOTE` is smote.SMOTE, re-exported.  Inputs live on a HIP device; there is no CPU path, and a shape the join
+kernel does not take raises `AgnnError`.
 
-Not here: `CadenceGNNNeighbor` and `CadenceGNNPytorch` and the join `LayerNorm(scatter_mean(x[src], dst,
-out=x.clone()))` between their encoder and `pool_mlp`; the three Lightning modules, their optimizers and schedulers;
-`CadenceAssistedPLModel`'s unpadding of a foreign encoder's output.  tests/cadence_ref.py states the two models and the join in
-float64, and tests/golden/cadence_*.npz hold what the reference's own classes compute, for whoever builds them."""
+Not here: the three Lightning modules, their optimizers and schedulers; `CadenceAssistedPLModel`'s unpadding of a
+foreign encoder's output."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
@@ -21,19 +21,22 @@ from . import pitch_spelling as _ps
 from . import smote as _smote
 from ._abi import AgnnError
 from .chord import act_norm_drop
-from .encoders import SAGEConv
-from .fused import norm_act
-from .graph import hetero_index
+from .embedding import embedding
+from .encoders import MetricalGNN, SAGEConv, _HybridMixin, _head
+from .fused import FusedSequential, norm_act
+from .graph import SegSpec, build_csr, hetero_index
 from .heads import multitask_cross_entropy
-from .linear import Linear, linear
+from .linear import Linear, linear, linear2
 from .metrics import MultiTaskMetrics
 from .smote import SMOTE
 
-__all__ = ["SMOTE", "GNN", "HierarchicalHeteroGraphSage", "cad_clf", "run_cad_clf", "balanced_cross_entropy", "cadence_training_loss",
-           "cadence_validation_loss", "cadence_metrics"]
+__all__ = ["SMOTE", "GNN", "HierarchicalHeteroGraphSage", "CadenceGNNNeighbor", "CadenceGNNPytorch", "JoinNorm", "JoinIndex", "join_index",
+           "pool_norm", "cad_clf", "run_cad_clf", "balanced_cross_entropy", "cadence_training_loss", "cadence_validation_loss",
+           "cadence_metrics"]
 
 BCE_MAX_CLASSES = _lib.CONSTS["AGNN_BCE_MAX_CLASSES"]
 _EDGE = ("n", "e", "n")
+_ONSET = ("note", "onset", "note")
 
 
 # ---- class-balanced cross entropy -----------------------------------------------------------------------------------------------
@@ -143,6 +146,210 @@ class HierarchicalHeteroGraphSage(_ps.HierarchicalHeteroGraphSage):
         x, last = self._run(x_dict, edge_index_dict, num_sampled_edges_dict, num_sampled_nodes_dict)
         trimmed = {et: (ei if last.get(et) is None else ei[:, :max(int(last[et]), 0)]) for et, ei in edge_index_dict.items()}
         return x, trimmed
+
+
+# ---- the join: onset mean-pool + LayerNorm in one launch --------------------------------------------------------------------------
+class JoinIndex:
+    """The two index structures of one edge list over n rows, from ONE agnn_csr_build: the edges by destination (rows =
+    `dst`, what the forward walks) and by source (the backward).  Messages flow src -> dst, PyG's direction."""
+
+    def __init__(self, n: int, src: torch.Tensor, dst: torch.Tensor):
+        if src.dim() != 1 or dst.dim() != 1 or src.shape != dst.shape or src.dtype != torch.int64 or dst.dtype != torch.int64:
+            raise AgnnError(f"pool_norm: src and dst must be int64 [E], got {tuple(src.shape)} {src.dtype} and {tuple(dst.shape)} {dst.dtype}")
+        _lib.require_gpu(src, dst)
+        self.n = int(n)
+        self.by_dst, self.by_src = build_csr([SegSpec(dst, src, self.n), SegSpec(src, dst, self.n)])
+
+
+_JOIN_CACHE: "Dict[tuple, JoinIndex]" = {}
+_JOIN_CACHE_MAX = 8
+
+
+def join_index(n: int, src: torch.Tensor, dst: torch.Tensor) -> JoinIndex:
+    """Build (or fetch) the index of a batch: keyed on identity and version of the two tensors, as chord.pool_index is."""
+    key = (int(n), src.data_ptr(), tuple(src.shape), src._version, dst.data_ptr(), tuple(dst.shape), dst._version)
+    hit = _JOIN_CACHE.get(key)
+    if hit is None:
+        hit = JoinIndex(n, src, dst)
+        if len(_JOIN_CACHE) >= _JOIN_CACHE_MAX:
+            _JOIN_CACHE.pop(next(iter(_JOIN_CACHE)))
+        _JOIN_CACHE[key] = hit
+        hit._keepalive = (src, dst)
+    return hit
+
+
+def clear_join_cache() -> None:
+    _JOIN_CACHE.clear()
+
+
+def _rel(csr):
+    return _lib.make_rels([dict(src=None, rowptr=csr.rowptr.data_ptr(), col=csr.col.data_ptr(), ld_src=0)])
+
+
+class _PoolJoin(torch.autograd.Function):
+    """u = the pooled rows, written by agnn_pool_norm_f32, which also leaves LayerNorm(u) and its statistics in `box` for the
+    consumer (`fused.norm_act(u, ln, pre=box)`: that node carries the LayerNorm's backward).  Backward: agnn_pool_bwd_f32 on du."""
+
+    @staticmethod
+    def forward(ctx, x, ix, pool_rows, col_limit, flags, gamma, beta, eps, box):
+        dev = x.device
+        n, H = x.shape
+        u = torch.empty((n, H), dtype=torch.float32, device=dev)
+        y = torch.empty((n, H), dtype=torch.float32, device=dev)
+        mean = torch.empty((max(n, 1),), dtype=torch.float32, device=dev)
+        rstd = torch.empty((max(n, 1),), dtype=torch.float32, device=dev)
+        inv_cnt = torch.empty((max(n, 1),), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().agnn_pool_norm_f32(_rel(ix.by_dst), x.data_ptr(), x.stride(0) if n else H, n, pool_rows, H, col_limit, flags,
+                                                  gamma.data_ptr(), beta.data_ptr(), float(eps), u.data_ptr(), H, y.data_ptr(), H,
+                                                  mean.data_ptr(), rstd.data_ptr(), inv_cnt.data_ptr(), _lib.stream_ptr(dev)),
+                   "agnn_pool_norm_f32")
+        box.extend([y, mean, rstd])
+        ctx.ix, ctx.cfg = ix, (pool_rows, col_limit, flags)
+        ctx.save_for_backward(inv_cnt)
+        return u
+
+    @staticmethod
+    def backward(ctx, du):
+        inv_cnt, = ctx.saved_tensors
+        pool_rows, col_limit, flags = ctx.cfg
+        du = _lib.rows16(du)
+        n, H = du.shape
+        dx = torch.empty((n, H), dtype=torch.float32, device=du.device)
+        _lib.check(_lib.load().agnn_pool_bwd_f32(_rel(ctx.ix.by_src), du.data_ptr(), du.stride(0) if n else H, inv_cnt.data_ptr(), n, pool_rows,
+                                                 H, col_limit, flags, dx.data_ptr(), H, _lib.stream_ptr(du.device)), "agnn_pool_bwd_f32")
+        return dx, None, None, None, None, None, None, None, None
+
+
+def pool_norm(x: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, ln: nn.LayerNorm, pool_rows: Optional[int] = None,
+              col_limit: Optional[int] = None, skip_self: bool = False, index: Optional[JoinIndex] = None) -> torch.Tensor:
+    """ln(scatter_mean(x[src], dst, dim=0, out=x.clone())) of both cadence models (models/cadence.py:204-205, :324-330) from one
+    launch (csrc/pooljoin.hip): x [n, H] fp32 on a HIP device, H a multiple of 4 in [4, 1024]; messages flow src -> dst.  Only
+    rows below `pool_rows` pool (default n), only sources below `col_limit` count (default n), `skip_self` drops self loops:
+    the reference's two mask compactions as kernel-side predicates.  `index`: a `join_index(n, src, dst)` built earlier.
+    There is one path: any other shape raises AgnnError."""
+    if x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32:
+        raise AgnnError(f"pool_norm: x must be an fp32 [n, H] matrix on a HIP device, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    n, H = int(x.shape[0]), int(x.shape[1])
+    if H < 4 or H % 4 != 0 or H > 1024:
+        raise AgnnError(f"pool_norm: H={H} must be a multiple of 4 in [4, 1024]")
+    if not ln.elementwise_affine or tuple(ln.normalized_shape) != (H,) or ln.weight.dtype != torch.float32 or ln.bias is None:
+        raise AgnnError(f"pool_norm: an affine fp32 LayerNorm over ({H},) expected, got {ln}")
+    _lib.require_gpu(x, src, dst, ln.weight)
+    pool_rows = n if pool_rows is None else min(int(pool_rows), n)
+    col_limit = n if col_limit is None else max(min(int(col_limit), n), 0)
+    if n > 0 and pool_rows < 1:
+        raise AgnnError(f"pool_norm: pool_rows={pool_rows} (at least one pooled row)")
+    if index is None:
+        index = join_index(n, src, dst)
+    elif index.n != n:
+        raise AgnnError(f"pool_norm: the index was built for {index.n} rows, x has {n}")
+    x = _lib.rows16(x)
+    gamma, beta = _lib.vec16(ln.weight.detach()), _lib.vec16(ln.bias.detach())
+    box: list = []
+    u = _PoolJoin.apply(x, index, pool_rows, col_limit, _lib.SPMM_SKIP_SELF if skip_self else 0, gamma, beta, ln.eps, box)
+    return norm_act(u, ln, pre=box)
+
+
+class JoinNorm(nn.LayerNorm):
+    """The models' `norm`: an `nn.LayerNorm` (same parameters, same `state_dict` keys) whose forward takes the onset edges and
+    runs the pooling in the same launch (a forward hook on it sees the join's output)."""
+
+    def forward(self, x, src, dst, pool_rows=None, col_limit=None, skip_self=False, index=None):
+        return pool_norm(x, src, dst, self, pool_rows, col_limit, skip_self, index)
+
+
+def _pool_mlp(hidden: int, dropout: float) -> FusedSequential:
+    return FusedSequential(Linear(hidden, hidden), nn.ReLU(), nn.LayerNorm(hidden), nn.Dropout(dropout), Linear(hidden, hidden))
+
+
+# ---- the two models ---------------------------------------------------------------------------------------------------------------
+class CadenceGNNNeighbor(nn.Module):
+    """models/cadence.py:179-226.  The join runs on the trimmed onset edges the stack returns, over all rows, self loops kept."""
+
+    def __init__(self, metadata, input_dim, hidden_dim, output_dim, num_layers, dropout=0.5):
+        super().__init__()
+        self.gnn = HierarchicalHeteroGraphSage(edge_types=[tuple(e) for e in metadata[1]], input_channels=input_dim, hidden_channels=hidden_dim,
+                                               out_channels=hidden_dim // 2, num_layers=num_layers)
+        hidden_dim = hidden_dim // 2
+        self.norm = JoinNorm(hidden_dim)
+        self.pool_mlp = _pool_mlp(hidden_dim, dropout)
+        self.cad_clf = cad_clf(hidden_dim, output_dim, dropout)
+
+    def onset_pool(self, x, edge_index_dict):
+        onset_index = edge_index_dict[_ONSET]
+        return self.pool_mlp(self.norm(x, onset_index[0], onset_index[1]))
+
+    def encode(self, x_dict, edge_index_dict, num_sampled_edges_dict=None, num_sampled_nodes_dict=None):
+        dev = _lib.require_gpu(*x_dict.values())
+        if self.training:
+            fused.advance_rng(dev)
+        x, edge_index_dict = self.gnn(x_dict, edge_index_dict, num_sampled_edges_dict=num_sampled_edges_dict,
+                                      num_sampled_nodes_dict=num_sampled_nodes_dict)
+        return self.onset_pool(x, edge_index_dict)
+
+    def forward(self, x_dict, edge_index_dict, num_sampled_edges_dict=None, num_sampled_nodes_dict=None):
+        x = self.encode(x_dict, edge_index_dict, num_sampled_edges_dict, num_sampled_nodes_dict)
+        return torch.softmax(self.clf(x), dim=-1)
+
+    def clf(self, x):
+        return run_cad_clf(self.cad_clf, x, self.training)
+
+
+class CadenceGNNPytorch(nn.Module, _HybridMixin):
+    """models/cadence.py:229-344 on encoders.MetricalGNN.  The targets are the first `batch_size` rows; the join pools over the
+    onset edges with both ends among them, self loops removed.  `use_pitch_spelling` is always set (the reference leaves it unset
+    when False) and `pitch_spelling` (int64 [n_notes], values in [0, 38)) is the last keyword of `encode` AND of `forward` (the
+    reference's `forward` never passes it and so cannot run); it is refused when needed and absent."""
+
+    def __init__(self, metadata, input_dim, hidden_dim, output_dim, num_layers, dropout=0.5, hybrid=False, use_pitch_spelling=True):
+        super().__init__()
+        self.gnn = MetricalGNN(input_channels=input_dim, hidden_channels=hidden_dim, output_channels=hidden_dim // 2, num_layers=num_layers,
+                               metadata=metadata, dropout=dropout, fast=True)
+        self.use_pitch_spelling = bool(use_pitch_spelling)
+        if self.use_pitch_spelling:
+            self.pitch_spelling_emb = nn.Sequential(nn.Embedding(38, input_dim), nn.LayerNorm(input_dim))
+            self.input_projection = FusedSequential(Linear(2 * input_dim, input_dim), nn.ReLU(), nn.LayerNorm(input_dim))
+        hidden_dim = hidden_dim // 2
+        self.norm = JoinNorm(hidden_dim)
+        self.hybrid = bool(hybrid)
+        if self.hybrid:
+            self._init_hybrid(input_dim, hidden_dim, num_layers, dropout, use_jk=False)
+        self.pool_mlp = _pool_mlp(hidden_dim, dropout)
+        self.cad_clf = cad_clf(hidden_dim, output_dim, dropout)
+
+    def encode(self, x_dict, edge_index_dict, batch_size, neighbor_mask_node, neighbor_mask_edge, batch_dict=None, pitch_spelling=None):
+        note = x_dict["note"]
+        dev = _lib.require_gpu(note)
+        batch_size = min(int(batch_size), int(note.shape[0]))
+        if self.training:
+            fused.advance_rng(dev)
+        if self.use_pitch_spelling:
+            if pitch_spelling is None:
+                raise AgnnError("CadenceGNNPytorch: use_pitch_spelling=True needs `pitch_spelling` (int64 [n_notes])")
+            emb, ln = self.pitch_spelling_emb
+            table = norm_act(emb.weight, ln)                          # the 38 rows normalised once, then gathered
+            note = self.input_projection(torch.cat((note, embedding(pitch_spelling, table)), dim=-1))
+            x_dict = {**x_dict, "note": note}
+        x = self.gnn(x_dict, edge_index_dict, neighbor_mask_node=neighbor_mask_node, neighbor_mask_edge=neighbor_mask_edge,
+                     batch_size=batch_size)
+        if self.hybrid:
+            batch_note = (torch.zeros(batch_size, dtype=torch.long, device=dev) if batch_dict is None else batch_dict["note"][:batch_size])
+            z = self.hybrid_forward(_head(note, batch_size), batch_note)          # on the current stream
+            w, E = self.cat_proj.weight, x.shape[1]
+            y = linear2(x, z, w, self.cat_proj.bias)
+            x = y if y is not None else linear(x, w[:, :E], self.cat_proj.bias, acc=linear(z, w[:, E:]))
+        onset_index = edge_index_dict[_ONSET]
+        x = self.norm(x, onset_index[0], onset_index[1], pool_rows=batch_size, col_limit=batch_size, skip_self=True)
+        return self.pool_mlp(x)
+
+    def forward(self, x_dict, edge_index_dict, batch_size, neighbor_mask_node=None, neighbor_mask_edge=None, batch_dict=None,
+                pitch_spelling=None):
+        """softmax of the logits.  Masks left at None mean zeros, as in the reference: nothing is trimmed."""
+        x = self.encode(x_dict, edge_index_dict, batch_size, neighbor_mask_node, neighbor_mask_edge, batch_dict, pitch_spelling)
+        return torch.softmax(self.clf(x), dim=-1)
+
+    def clf(self, x):
+        return run_cad_clf(self.cad_clf, x, self.training)
 
 
 # ---- the Lightning steps, as functions ------------------------------------------------------------------------------------------

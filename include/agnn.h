@@ -216,6 +216,28 @@ int agnn_pool_cat_norm_f32(const agnn_rel_t* rel /* (host) */, const float* x, i
 int agnn_pool_cat_bwd_f32(const agnn_rel_t* rel_t /* (host) */, const float* du, int64_t ld_du, const float* inv_cnt, int64_t n,
                           int64_t pool_rows, int32_t H, float* dx, int64_t ld_dx, agnn_stream_t stream);
 
+/* The join of the cadence models (ref: models/cadence.py:204-205 and :324-330, `LayerNorm(scatter_mean(x[src], dst, out=x.clone()))`),
+ * csrc/pooljoin.hip: one wave per row, one launch.  For i < n:
+ *     u_i = i < pool_rows ? (x_i + sum_{valid p in row i} x[col[p]]) / max(cnt_i, 1) : x_i          -> u [n, H]
+ *           (valid(p) = 0 <= col < min(col_limit, n) && !(SKIP_SELF && col == i); neighbours summed in CSR order)
+ *     y_i = LayerNorm_eps(u_i) * gamma + beta                                                         -> y [n, H], mean [n], rstd [n]
+ *           (statistics centred twice: exact to fp32 rounding of the deviations also where the row's level dwarfs its spread)
+ *     inv_cnt[i] = 1 / max(cnt_i, 1)                                                                  (1 for i >= pool_rows)
+ * (u, mean, rstd) are what agnn_norm_act_bwd_f32 (seg = H, no flags) takes as (x, mean, rstd).
+ * `rel`: rowptr / col (/ rowend) of the by-destination index with at least pool_rows rows; its src, ld_src and colscale are
+ * ignored, ew must be NULL.  H any multiple of 4 in [4, 1024]; 1 <= pool_rows <= n; n == 0: nothing is done.  flags: AGNN_SPMM_SKIP_SELF
+ * or 0.  u and y must not be x. */
+int agnn_pool_norm_f32(const agnn_rel_t* rel /* (host) */, const float* x, int64_t ld_x, int64_t n, int64_t pool_rows, int32_t H,
+                       int32_t col_limit, uint32_t flags, const float* gamma, const float* beta, float eps, float* u, int64_t ld_u,
+                       float* y, int64_t ld_y, float* mean, float* rstd, float* inv_cnt, agnn_stream_t stream);
+/* The pooling's backward behind the LayerNorm's (du [n, H] from agnn_norm_act_bwd_f32), one launch:
+ *     dx_i = (i < pool_rows ? inv_cnt[i] : 1) * du_i + sum_{valid p in row i of rel_t} inv_cnt[col[p]] * du[col[p]]
+ * `rel_t`: the transposed (by-source) index with at least min(col_limit, n) rows; valid(p) = 0 <= col < pool_rows &&
+ * !(SKIP_SELF && col == i); rows at or beyond min(col_limit, n) were nobody's neighbour and take their own term only.  Same
+ * col_limit and flags as the forward call.  dx must not be du. */
+int agnn_pool_bwd_f32(const agnn_rel_t* rel_t /* (host) */, const float* du, int64_t ld_du, const float* inv_cnt, int64_t n,
+                      int64_t pool_rows, int32_t H, int32_t col_limit, uint32_t flags, float* dx, int64_t ld_dx, agnn_stream_t stream);
+
 /* Class-balanced cross entropy, the loss of the cadence models' validation steps (ref: models/cadence.py:425-434 and :535-544,
  * `weight = 1 / (bincount(y) + 1e-6); F.cross_entropy(logits, y, weight=weight)`), csrc/balce.hip:
  *     count_c = #{r : y_r == c},      w_c = 1 / (count_c + eps_w)

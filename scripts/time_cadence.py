@@ -1,9 +1,12 @@
 #!/usr/bin/env python
 """Time the class-balanced cross entropy (`cadence.balanced_cross_entropy`, csrc/balce.hip) on [16000, 5], value and gradient, against
-the torch composition of the reference's validation step: bincount, reciprocal, F.cross_entropy(weight=...).  One GPU, same inputs,
-one process.  Protocol: hipEvent pairs around every call, WARMUP untimed iterations, ITERS timed ones, the sides alternating
-iteration by iteration; median and p10 / p90 in microseconds.  Called eagerly, both sides are bound by the host's issue time of their
-launches, not by bytes: the figures compare launch chains.
+the torch composition of the reference's validation step: bincount, reciprocal, F.cross_entropy(weight=...); and the cadence models'
+join (`cadence.pool_norm`, csrc/pooljoin.hip) on [16000, 128] and [16000, 256] with 0 .. 3 in-neighbours per row, value and gradient
+(`torch.autograd.grad` of a fixed cotangent), against the composition of the library's own general kernels, written here only:
+`ops.aggregate(AggSpec(mean, shared_slot, skip_self, col_limit), self_t=x)` -> `fused.norm_act`.  One GPU, same inputs, one process.
+Protocol: hipEvent pairs around every call, WARMUP untimed iterations, ITERS timed ones, the sides alternating iteration by
+iteration; median and p10 / p90 in microseconds.  Every call is eager: nothing here is captured into a graph.  Called eagerly,
+the sides are bound by the host's issue time of their launches, not by bytes: the figures compare launch chains.
 
     python scripts/time_cadence.py [--out FILE]
 """
@@ -71,6 +74,36 @@ def loss_rows(n, C, lines):
         lines.append(row(f"balanced cross entropy [{n}, {C}], value and gradient", s, st[s], n * (8 * C + 8), "logits in, gradient out, labels"))
 
 
+def join_rows(n, H, lines):
+    """The join at `join_graph`-like degree: every row has 0 .. 3 in-neighbours, drawn from all rows."""
+    from analysisgnn_amd import cadence, fused, ops
+    g = torch.Generator().manual_seed(n + H)
+    dst = torch.repeat_interleave(torch.arange(n), torch.randint(0, 4, (n,), generator=g))
+    src = torch.randint(0, n, (int(dst.numel()),), generator=g)
+    src, dst = src.to(DEV), dst.to(DEV)
+    x = torch.randn(n, H, generator=g).to(DEV).requires_grad_(True)
+    cot = torch.randn(n, H, generator=g).to(DEV)
+    ln = torch.nn.LayerNorm(H).to(DEV)
+    ix = cadence.join_index(n, src, dst)
+    spec = ops.AggSpec(fwd=[ix.by_dst], bwd=[ix.by_src], src_id=[0], n_rows=n, mean=True, shared_slot=True, skip_self=True, col_limit=n)
+    leaves = [x, ln.weight, ln.bias]
+
+    def ours():
+        return torch.autograd.grad(cadence.pool_norm(x, src, dst, ln, n, n, True, index=ix), leaves, cot)
+
+    def composition():
+        return torch.autograd.grad(fused.norm_act(ops.aggregate(spec, [x], self_t=x), ln), leaves, cot)
+    for a, b in zip(ours(), composition()):
+        assert float((a - b).abs().max()) <= 1e-4 * float(b.abs().max()), "the two sides disagree"
+    st = timed({"kernel": ours, "composition": composition})
+    deg = float(dst.numel()) / n
+    # forward: x read (1 + deg) times, u and y written; backward: dy and u read, du written, du read (1 + deg) times, dx written
+    nbytes = int(n * H * 4 * (2 * (1 + deg) + 6))
+    for s in ("kernel", "composition"):
+        lines.append(row(f"join [{n}, {H}], {deg:.2f} in-neighbours per row, value and gradient", s, st[s], nbytes,
+                         "x and du read 1 + deg times; u, y, du, dx written; dy, u read"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
@@ -78,6 +111,8 @@ def main():
     assert torch.cuda.is_available()
     lines = []
     loss_rows(16000, 5, lines)
+    join_rows(16000, 128, lines)
+    join_rows(16000, 256, lines)
     head = [f"{torch.cuda.get_device_name(0)}; WARMUP {WARMUP}, ITERS {ITERS}, sides alternating", "",
             "| call | side | median µs | p10 .. p90 µs | bytes | floor at 8 TB/s, µs |", "|---|---|---|---|---|---|"]
     text = "\n".join(head + lines) + "\n"
